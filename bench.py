@@ -12,6 +12,14 @@ max-over-ranks timing use torch.distributed).  Ranks: either an outer
 starts the N ranks itself (a torch.distributed.run child, 127.0.0.1) before any
 GPU call and exits with their status.
 
+A plain run sets up, warms up, times the K steps and prints the line (metric,
+value, unit, ms_per_step, the timed steps' kernel times and roofline).  --full
+adds every other leg to the line as before: the device index rebuild, the
+per-kernel split, append, small records, host path, C5 reference, index load,
+CPU baselines and the C4 merge checks (each can be dropped with its --no-*
+option).  --dump-outputs DIR writes what the last timed step returned
+(dump_outputs).
+
 Workloads (BASELINE.json configs):
   c2 (default): 16 files x 256 MiB, key 0x00||%09d, 256-B random values -> 276-B records
   c1: one 64 MiB file of 1 KiB values (CPU plumbing config; also runnable here)
@@ -563,6 +571,76 @@ def dry_protocol(args, rank, world):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE_TUPLES = 1 << 18    # 262144 tuples x 12 words x 8 B = 24 MiB
+DUMP_SAMPLE_BYTES = 1 << 19     # per byte sample: index + bytes = 8 MiB as float64
+DUMP_SEED = 0x434C59
+
+
+def _dump_sample(n, k):
+    """A fixed sample of k of n positions (all of them when n <= k), ascending."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(d, rank, world, torch, wl, first, res, need, merge_info):
+    """--dump-outputs DIR: what the last timed step handed back, as float64
+    DIR/<name>.npy (every value an integer of magnitude below 2^53, so exact,
+    about 45 MB at the most over all ranks: rank r > 0 writes
+    <name>.rank<r>.npy and the samples shrink to 1/world of their size).  The
+    inputs are the same from run to run (fixed seeds), so two builds can be
+    compared array for array.
+      scan_needed [1], scan_file_first / scan_n_records / scan_end_offset /
+      scan_status [files]: cly_scan_device's host results;
+      scan_tuple_index [S], scan_tuples [S, 12]: a fixed sample of S of the
+      emitted 48-byte index tuples, as their 12 little-endian 32-bit words;
+      scan_tuple_word_sums [12, 2]: over ALL emitted tuples, the sums of each
+      word's low and high 16 bits;
+    c4 only (cly_merge_device): merge_counts [n_live, n_reencoded, n_out_files,
+      hint_bytes], merge_out_lens [files], merge_file_byte_sums [files],
+      merge_byte_index / merge_bytes and hint_byte_index / hint_bytes: fixed
+      samples of the merged files' bytes (position k * DataFileSize + offset)
+      and of the hint file's, merge_hint_byte_sum [1]."""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if rank == 0 else ".rank%d" % rank
+
+    def save(name, a):
+        np.save(os.path.join(d, name + sfx + ".npy"), np.asarray(a, dtype=np.float64))
+
+    save("scan_needed", [need])
+    save("scan_file_first", first)
+    save("scan_n_records", [r.n_records for r in res])
+    save("scan_end_offset", [r.end_offset for r in res])
+    save("scan_status", [r.status for r in res])
+    words = wl.d_out[: need * 48].view(torch.int32).view(need, 12)
+    idx = _dump_sample(need, DUMP_SAMPLE_TUPLES // world)
+    save("scan_tuple_index", idx)
+    save("scan_tuples", words[torch.from_numpy(idx).to(words.device)].cpu().numpy().view(np.uint32))
+    sums = np.zeros((12, 2))
+    for a in range(0, need, 1 << 24):          # chunks bound the int64 temporaries
+        w = words[a:a + (1 << 24)].to(torch.int64)
+        sums[:, 0] += (w & 0xFFFF).sum(0).cpu().numpy()
+        sums[:, 1] += ((w >> 16) & 0xFFFF).sum(0).cpu().numpy()
+    save("scan_tuple_word_sums", sums)
+    if wl.name != "c4":
+        return
+    lens, hb = merge_info["out_lens"], merge_info["hint_bytes"]
+    save("merge_counts", [merge_info[k] for k in ("n_live", "n_reencoded", "n_out_files", "hint_bytes")])
+    save("merge_out_lens", lens)
+    save("merge_file_byte_sums", [int(wl.d_merge[k * DATA_FILE_SIZE:k * DATA_FILE_SIZE + ln].sum(dtype=torch.int64))
+                                  for k, ln in enumerate(lens)])
+    save("merge_hint_byte_sum", [int(wl.d_hint[:hb].sum(dtype=torch.int64))])
+    ends = np.cumsum(lens)
+    idx = _dump_sample(int(ends[-1]) if len(lens) else 0, DUMP_SAMPLE_BYTES // world)
+    k = np.searchsorted(ends, idx, side="right")
+    pos = k * DATA_FILE_SIZE + (idx - (ends[k] - np.asarray(lens, np.int64)[k])) if len(idx) else idx
+    save("merge_byte_index", pos)
+    save("merge_bytes", wl.d_merge[torch.from_numpy(pos).to(wl.d_merge.device)].cpu().numpy())
+    idx = _dump_sample(hb, DUMP_SAMPLE_BYTES // world)
+    save("hint_byte_index", idx)
+    save("hint_bytes", wl.d_hint[torch.from_numpy(idx).to(wl.d_hint.device)].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -578,9 +656,20 @@ def main():
     ap.add_argument("--no-host-path", action="store_true", help="skip the host-buffer (PCIe-inclusive) leg")
     ap.add_argument("--verify", action="store_true", help="check one file against the oracle after timing")
     ap.add_argument("--dry-protocol", action="store_true", help="rank protocol only, on the CPU (launcher tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: device index rebuild, per-kernel split, "
+                         "append, small records, host path, C5 reference, index load, CPU baselines, the C4 merge's "
+                         "rescan / hint scan / post-merge open (the --no-* options subtract from these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_post_merge_open = args.no_c5_leg = args.no_cpu_baseline = args.no_host_path = True
     # Ranks: under torch.distributed.run WORLD_SIZE is set and must equal
     # --gpus; without it, --gpus N > 1 starts its own N ranks (before any GPU
     # call in this process) and exits with their status.
@@ -638,21 +727,24 @@ def main():
     # index rebuild (db.loadIndex's String/ListMeta indexes) over the scanned
     # tuples on the device, before the timed steps: the device-resident
     # index-load time = scan + index; for c4 its live bytes drive the merge
-    first, res, st, need = sc.scan_device(wl.dev_files, wl.d_out.data_ptr(), wl.out_cap)
-    st = sc.scan_device(wl.dev_files, wl.d_out.data_ptr(), wl.out_cap)[2]
-    d_state = torch.empty(max(1, need), dtype=torch.uint8, device="cuda")
-    ixr = sc.index_device(wl.dev_files, wl.d_out.data_ptr(), first, res, d_state.data_ptr())
-    ixr = sc.index_device(wl.dev_files, wl.d_out.data_ptr(), first, res, d_state.data_ptr())
-    index_info = {"index_ms": round(ixr.index_ms, 3), "scan_ms": round(st.total_ms, 3),
-                  "device_index_load_ms": round(st.total_ms + ixr.index_ms, 3),
-                  "keys_live": int(ixr.n_live), "records_applied": int(ixr.n_applied),
-                  "hash_collisions": int(ixr.n_collisions)}
-    if args.config == "c4":
-        # the merge's live bytes are the index's; they must equal the workload's
-        index_info["matches_workload_live"] = bool((d_state[:need].cpu().numpy() == wl.live_np).all())
-        wl.live = d_state
-    else:
-        del d_state
+    # (a plain run needs it only for c4, whose step consumes the live bytes)
+    index_info = None
+    if args.full or args.config == "c4":
+        first, res, st, need = sc.scan_device(wl.dev_files, wl.d_out.data_ptr(), wl.out_cap)
+        st = sc.scan_device(wl.dev_files, wl.d_out.data_ptr(), wl.out_cap)[2]
+        d_state = torch.empty(max(1, need), dtype=torch.uint8, device="cuda")
+        ixr = sc.index_device(wl.dev_files, wl.d_out.data_ptr(), first, res, d_state.data_ptr())
+        ixr = sc.index_device(wl.dev_files, wl.d_out.data_ptr(), first, res, d_state.data_ptr())
+        index_info = {"index_ms": round(ixr.index_ms, 3), "scan_ms": round(st.total_ms, 3),
+                      "device_index_load_ms": round(st.total_ms + ixr.index_ms, 3),
+                      "keys_live": int(ixr.n_live), "records_applied": int(ixr.n_applied),
+                      "hash_collisions": int(ixr.n_collisions)}
+        if args.config == "c4":
+            # the merge's live bytes are the index's; they must equal the workload's
+            index_info["matches_workload_live"] = bool((d_state[:need].cpu().numpy() == wl.live_np).all())
+            wl.live = d_state
+        else:
+            del d_state
 
     for _ in range(args.warmup):
         step()
@@ -680,13 +772,17 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt, scan_dev_ms, crc_ms = float(t[0]), float(t[1]), float(t[2])
-    # the link / k_emit / k_fin split from one more scan call with per-kernel
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, torch, wl, first, res, need, merge_info)
+    # --full: the link / k_emit / k_fin split from one more scan call with per-kernel
     # markers (cly_dbg_set bit 2: a marker between kernels costs ~5 us, so the
     # timed steps keep only the k_scan and whole-call ones)
-    sc.lib.cly_dbg_set(sc.ctx, 4)
-    sc.scan_device(wl.dev_files, wl.d_out.data_ptr(), wl.out_cap)
-    kdiag = sc.kernel_ms()
-    sc.lib.cly_dbg_set(sc.ctx, 0)
+    kdiag = None
+    if args.full:
+        sc.lib.cly_dbg_set(sc.ctx, 4)
+        sc.scan_device(wl.dev_files, wl.d_out.data_ptr(), wl.out_cap)
+        kdiag = sc.kernel_ms()
+        sc.lib.cly_dbg_set(sc.ctx, 0)
     ms = dt / args.steps * 1e3
     total_bytes = wl.bytes * world
     total_recs = recs * world
@@ -704,10 +800,10 @@ def main():
                    "parallelism": "files sharded by fid range, %d GPU(s), no collective" % world},
         "mrecords_per_s": round(total_recs / (ms / 1e3) / 1e6, 2),
         "kernel": {"k_scan_ms": round(kms["k_scan"] / args.steps, 4), "all_ms": round(kms["all"] / args.steps, 4),
-                   **{k + "_ms": round(kdiag[k], 4) for k in ("link", "k_emit", "k_fin", "retry")},
+                   **({k + "_ms": round(kdiag[k], 4) for k in ("link", "k_emit", "k_fin", "retry")} if kdiag else {}),
                    "device_ms": round(scan_dev_ms, 4), "passes": passes, "build": build_info(),
                    "note": "k_scan_ms, all_ms: the timed steps' averages (HIP events); link/k_emit/k_fin: one more "
-                           "call with per-kernel markers"},
+                           "call with per-kernel markers (--full only)"},
         "roofline": {"bound": "hbm", "kernel": "k_scan", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": measured_traffic(args.config),
@@ -718,7 +814,8 @@ def main():
                              "FETCH_SIZE/WRITE_SIZE passes of this build (profiles/*_traffic.json), null if none"},
         "parity_ok": ok,
     }
-    out["index"] = index_info
+    if index_info:
+        out["index"] = index_info
     if args.config == "c2" and rank == 0 and world == 1 and not args.no_host_path:
         out["append"] = append_leg(wl, sc, first, torch)
         out["small_records"] = small_records_leg(sc, torch)
@@ -728,31 +825,32 @@ def main():
         mms = merge_ms[0] / args.steps
         mi["merge_ms"] = round(mms, 4)
         mi["merge_io_gbs"] = round((mi["out_bytes"] * 2 + mi["hint_bytes"]) / (mms / 1e3) / 1e9, 1)
-        # size-independent checks: the live count, and a rescan of the merge output
-        # (every merged record decodes, keys carry NO_TX_ID, files end cleanly) and of the hint file
-        mfiles = [(wl.d_merge.data_ptr() + k * DATA_FILE_SIZE, lens[k], k) for k in range(len(lens))]
-        cap = mi["n_live"] + 1024
-        d2 = torch.empty(cap * 48, dtype=torch.uint8, device="cuda")
-        f2, r2, _, n2 = sc.scan_device(mfiles, d2.data_ptr(), cap)
-        hf = [(wl.d_hint.data_ptr(), mi["hint_bytes"], 0)]
-        f3, r3, _, n3 = sc.scan_device(hf, d2.data_ptr(), cap)
-        # loadIndexFromHintFile's scan (merge.go:257-287) of the merge's hint
-        # file: ~24-B records, every tile past CAP_T (spill chunks)
-        ht, hk, hn, hres = timed_scans(sc, hf, d2.data_ptr(), cap)
-        mi["hint_scan"] = {"value": round(mi["hint_bytes"] / ht / 2**30, 2), "unit": "GiB/s",
-                           "ms": round(ht * 1e3, 3), "k_scan_ms": round(hk, 3), "records": int(hn),
-                           "tb_per_s": round(mi["hint_bytes"] / ht / 1e12, 3)}
-        mi["rescan_ok"] = bool(n2 == mi["n_live"] and all(r.status == 0 for r in r2) and n3 == mi["n_live"]
-                               and r3[0].status == 0)
+        if args.full:
+            # size-independent checks: the live count, and a rescan of the merge output
+            # (every merged record decodes, keys carry NO_TX_ID, files end cleanly) and of the hint file
+            mfiles = [(wl.d_merge.data_ptr() + k * DATA_FILE_SIZE, lens[k], k) for k in range(len(lens))]
+            cap = mi["n_live"] + 1024
+            d2 = torch.empty(cap * 48, dtype=torch.uint8, device="cuda")
+            f2, r2, _, n2 = sc.scan_device(mfiles, d2.data_ptr(), cap)
+            hf = [(wl.d_hint.data_ptr(), mi["hint_bytes"], 0)]
+            f3, r3, _, n3 = sc.scan_device(hf, d2.data_ptr(), cap)
+            # loadIndexFromHintFile's scan (merge.go:257-287) of the merge's hint
+            # file: ~24-B records, every tile past CAP_T (spill chunks)
+            ht, hk, hn, hres = timed_scans(sc, hf, d2.data_ptr(), cap)
+            mi["hint_scan"] = {"value": round(mi["hint_bytes"] / ht / 2**30, 2), "unit": "GiB/s",
+                               "ms": round(ht * 1e3, 3), "k_scan_ms": round(hk, 3), "records": int(hn),
+                               "tb_per_s": round(mi["hint_bytes"] / ht / 1e12, 3)}
+            mi["rescan_ok"] = bool(n2 == mi["n_live"] and all(r.status == 0 for r in r2) and n3 == mi["n_live"]
+                                   and r3[0].status == 0)
+            del d2
         out["merge"] = mi
-        del d2
         if rank == 0 and world == 1 and not args.no_post_merge_open:
             torch.cuda.empty_cache()
             try:
                 out["post_merge_open"] = post_merge_open_leg(wl, sc, torch, lens, mi["hint_bytes"], mi["n_live"])
             except Exception as e:     # reported in the line, not fatal to it
                 out["post_merge_open"] = {"error": repr(e)}
-        out["parity_ok"] = bool(ok and mi["n_live"] == wl.n_live and mi["rescan_ok"]
+        out["parity_ok"] = bool(ok and mi["n_live"] == wl.n_live and mi.get("rescan_ok", True)
                                 and index_info["matches_workload_live"])
     if args.verify and rank == 0:
         from oracle import cly_oracle as co

@@ -1,5 +1,5 @@
 """k_scan launches of bench.py's timed loop from a rocprofv3 kernel trace of
-the bench itself (`rocprofv3 --kernel-trace --stats -- python3 bench.py`):
+the bench itself (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full`):
 the k_scan launches in issue order are split into runs of similar duration
 (within 25 % of the run's first); the longest run holds the index-rebuild
 scans, the warm-up and the timed steps, of which the last STEPS (default 20)

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 D=gpurun_out/c15
 mkdir -p $D
 export TMPDIR=/tmp
-timeout -k 10 500 python -u bench.py --config c5 --no-host-path --no-cpu-baseline > $D/bench_c5.json 2> $D/bench_c5.err || exit $?
+timeout -k 10 500 python -u bench.py --full --config c5 --no-host-path --no-cpu-baseline > $D/bench_c5.json 2> $D/bench_c5.err || exit $?
 tail -1 $D/bench_c5.json | cut -c1-400
-timeout -k 10 300 python -u bench.py --config c1 --no-host-path > $D/bench_c1.json 2> $D/bench_c1.err || exit $?
+timeout -k 10 300 python -u bench.py --full --config c1 --no-host-path > $D/bench_c1.json 2> $D/bench_c1.err || exit $?
 tail -1 $D/bench_c1.json | cut -c1-400

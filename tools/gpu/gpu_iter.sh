@@ -11,5 +11,5 @@ timeout -k 10 900 python -u -m pytest tests -q -x --timeout 300 --timeout-method
 rc=$?; echo "pytest rc=$rc"; tail -3 $D/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
 bash tools/gpu/gpu_ab.sh $1 libclyscan.so || exit $?
-timeout -k 10 400 python -u bench.py > $D/bench_c2.json 2> $D/bench_c2.err || exit $?
+timeout -k 10 400 python -u bench.py --full > $D/bench_c2.json 2> $D/bench_c2.err || exit $?
 python3 -c "import json,sys; b=json.loads(open('$D/bench_c2.json').read().strip().splitlines()[-1]); print(b['value'], b['kernel'], b.get('small_records'), b.get('index_load'))"

@@ -10,8 +10,8 @@ mkdir -p $D
 export TMPDIR=/tmp
 bash tools/gpu/gpu_cmp.sh > $D/cmp.log 2>&1 || exit $?
 cp gpurun_out/cmp/bench_c2.json $D/bench_c2.json
-timeout -k 10 400 python -u bench.py --config c4 --no-host-path --no-cpu-baseline > $D/bench_c4.json 2> $D/bench_c4.err || exit $?
-timeout -k 10 400 python -u bench.py --config c3 --no-host-path --no-cpu-baseline > $D/bench_c3.json 2> $D/bench_c3.err || exit $?
+timeout -k 10 400 python -u bench.py --full --config c4 --no-host-path --no-cpu-baseline > $D/bench_c4.json 2> $D/bench_c4.err || exit $?
+timeout -k 10 400 python -u bench.py --full --config c3 --no-host-path --no-cpu-baseline > $D/bench_c3.json 2> $D/bench_c3.err || exit $?
 S1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS"
 S2="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_LDS_BANK_CONFLICT"
 for cfg in c2 c3 c4; do
@@ -22,10 +22,10 @@ for cfg in c2 c3 c4; do
     timeout -s KILL 300 rocprofv3 --pmc $s --kernel-trace --output-format csv -d $D/${cfg}_p$i -o run -- python3 tools/scan_once.py $cfg 2 > $D/${cfg}_p$i.log 2>&1 || exit $?
   done
 done
-timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/c4m_stats -o run -- python3 bench.py --config c4 --steps 3 --warmup 1 --no-host-path --no-cpu-baseline > $D/c4m_stats.log 2>&1 || exit $?
+timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/c4m_stats -o run -- python3 bench.py --full --config c4 --steps 3 --warmup 1 --no-host-path --no-cpu-baseline > $D/c4m_stats.log 2>&1 || exit $?
 i=0
 for s in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout -s KILL 300 rocprofv3 --pmc $s --kernel-trace --output-format csv -d $D/c4m_p$i -o run -- python3 bench.py --config c4 --steps 1 --warmup 1 --no-host-path --no-cpu-baseline > $D/c4m_p$i.log 2>&1 || exit $?
+  timeout -s KILL 300 rocprofv3 --pmc $s --kernel-trace --output-format csv -d $D/c4m_p$i -o run -- python3 bench.py --full --config c4 --steps 1 --warmup 1 --no-host-path --no-cpu-baseline > $D/c4m_p$i.log 2>&1 || exit $?
 done
 echo done

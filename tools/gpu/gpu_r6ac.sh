@@ -14,5 +14,5 @@ for c in c2 c5 c3; do
   timeout -k 10 300 python -u tools/wall_ab.py $c libexp_419bf65.so libclyscan.so > $D/wall_${c}_ba.log 2>&1 || exit $?
 done
 grep -h "wall" $D/wall_*.log
-timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/bench_stats -o run -- python3 bench.py --no-host-path --no-cpu-baseline --no-c5-leg > $D/bench_under_rocprof.json 2> $D/bench_stats.err || exit $?
+timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/bench_stats -o run -- python3 bench.py --full --no-host-path --no-cpu-baseline --no-c5-leg > $D/bench_under_rocprof.json 2> $D/bench_stats.err || exit $?
 echo done

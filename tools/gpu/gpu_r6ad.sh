@@ -14,5 +14,5 @@ for c in c2 c1 c5; do
   timeout -k 10 300 python -u tools/wall_ab.py $c libexp_82f6533.so libclyscan.so > $D/wall_${c}_ba.log 2>&1 || exit $?
 done
 grep -h "wall" $D/wall_*.log
-timeout -k 10 400 python -u bench.py --no-host-path --no-cpu-baseline --no-c5-leg > $D/bench_c2.json 2> $D/bench_c2.err || exit $?
+timeout -k 10 400 python -u bench.py --full --no-host-path --no-cpu-baseline --no-c5-leg > $D/bench_c2.json 2> $D/bench_c2.err || exit $?
 tail -c 700 $D/bench_c2.json

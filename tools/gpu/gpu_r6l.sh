@@ -14,6 +14,6 @@ timeout -k 10 300 python -u tools/index_once.py c4 libclyscan.so libexp_fd8e900.
 timeout -k 10 300 python -u tools/index_once.py c2 libclyscan.so libexp_fd8e900.so > $D/ix_c2.log 2>&1 || exit $?
 grep index_ms $D/ix_c4.log $D/ix_c2.log
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/ix_stats -o run -- python3 tools/index_once.py c4 libclyscan.so > $D/ix_stats.log 2>&1 || exit $?
-timeout -k 10 500 python -u bench.py --config c4 --no-host-path --no-cpu-baseline > $D/bench_c4.json 2> $D/bench_c4.err || exit $?
+timeout -k 10 500 python -u bench.py --full --config c4 --no-host-path --no-cpu-baseline > $D/bench_c4.json 2> $D/bench_c4.err || exit $?
 tail -c 1500 $D/bench_c4.json
 echo done

@@ -20,6 +20,7 @@ from ._abi import (END_EOF, END_TORN, END_ZERO, ERR_CRC, ERR_OFFSET, ERR_TRUNC5,
                    POS_DTYPE, REC_IN_DTYPE, TUPLE_DTYPE)
 
 __all__ = ["POS_DTYPE", "Scanner", "DataFile", "LogRecord", "LogPos", "ScanResult", "ScanError", "MergeResult",
+           "ReadResult",
            "ErrInvalidCRC", "TUPLE_DTYPE", "STATUS_NAMES"]
 
 # data/logRecord.go:10-16 / :20-26
@@ -109,6 +110,44 @@ class ScanResult:
             raise ScanError(st, "at offset %d" % self.end_offset[i])
 
 
+class ReadResult:
+    """Output of Scanner.read (cly_read): per position its status (int32:
+    _abi.READ_REC, _abi.READ_NOFILE or a ReadLogRecord terminal), its tuple
+    (TUPLE_DTYPE), val_off (n + 1 offsets into values) and the values of the
+    READ_REC positions back to back (None after values=False)."""
+
+    def __init__(self, files, positions, status, tuples, val_off, values, r):
+        self.files = {f.fid: f for f in files}
+        self.positions = positions
+        self.status, self.tuples, self.val_off, self.values = status, tuples, val_off, values
+        self.result = r
+
+    def record(self, i):
+        """The LogRecord ReadLogRecord returns at position i (a tombstone
+        included: getLogRecordByPos's ErrKeyNotFound for it is the caller's, by
+        .type); raises as the scan path does: ErrInvalidCRC, ScanError for
+        the reference's panics, EOFError for io.EOF, KeyError for a file id
+        that is not open."""
+        st = int(self.status[i])
+        where = "fid %d offset %d" % (int(self.positions[i]["fid"]), int(self.positions[i]["offset"]))
+        if st == _abi.READ_NOFILE:
+            raise KeyError(where)
+        if st == ERR_CRC:
+            raise ErrInvalidCRC(st, "at " + where)
+        if st < 0:
+            raise ScanError(st, "at " + where)
+        if st != _abi.READ_REC:
+            raise EOFError("%s at %s" % (STATUS_NAMES.get(st, st), where))
+        t = self.tuples[i]
+        o, h, ks = int(t["offset"]), int(t["header_size"]), int(t["key_size"])
+        key = self.files[int(t["fid"])].data[o + h:o + h + ks].tobytes()
+        if self.values is not None:
+            val = self.values[int(self.val_off[i]):int(self.val_off[i + 1])].tobytes()
+        else:
+            val = self.files[int(t["fid"])].data[o + h + ks:o + h + ks + int(t["value_size"])].tobytes()
+        return LogRecord(key, val, int(t["type"]), int(t["data_type"]), int(t["expiration"]))
+
+
 class MergeResult:
     """Output of Scanner.merge: the merge DB's data files (fid k = files[k]), the
     hint-index file, and the counters of cly_merge_result."""
@@ -183,6 +222,50 @@ class Scanner:
         n = len(files)
         return ScanResult(files, out[:int(need.value)], [int(first[i]) for i in range(n)],
                           [res[i] for i in range(n)], st)
+
+    def read(self, files, positions, values=True):
+        """getLogRecordByPos (db.go:676-704) over a batch, host buffers in and
+        out (cly_read): positions = POS_DTYPE array or [(fid, offset)].  Every
+        position is one ReadLogRecord, CRC included; values=False is the
+        verify-and-size pass.  Returns a ReadResult."""
+        files = list(files)
+        arr = self._file_array(files)
+        if isinstance(positions, np.ndarray) and positions.dtype == POS_DTYPE:
+            pos = np.ascontiguousarray(positions)
+        else:
+            pos = np.zeros(len(positions), POS_DTYPE)
+            for i, (fid, off) in enumerate(positions):
+                pos[i]["fid"], pos[i]["offset"] = fid, off
+        n = len(pos)
+        tup = np.zeros(max(1, n), TUPLE_DTYPE)
+        status = np.zeros(max(1, n), np.int32)
+        voff = np.zeros(n + 1, np.uint64)
+        r = _abi.ClyReadResult()
+        args = (self.ctx, arr, len(files), pos.ctypes.data if n else None, n, tup.ctypes.data, status.ctypes.data,
+                voff.ctypes.data)
+        rc = self.lib.cly_read(*args, None, 0, ctypes.byref(r))
+        vals = None
+        if rc == 0 and values:
+            vals = np.zeros(max(1, int(r.value_bytes)), np.uint8)
+            rc = self.lib.cly_read(*args, vals.ctypes.data, int(r.value_bytes), ctypes.byref(r))
+            vals = vals[:int(r.value_bytes)]
+        if rc != 0:
+            raise ScanError(rc, self.lib.cly_strerror(rc).decode())
+        return ReadResult(files, pos, status[:n], tup[:n], voff, vals, r)
+
+    def read_device(self, dev_files, d_pos, n, d_tuples, d_status, d_val_off, d_values, values_cap, stream=None):
+        """Device-resident read by position (cly_read_device): dev_files =
+        [(device_ptr, len, fid)], the rest device pointers (d_tuples and
+        d_values may be None).  Returns (rc, ClyReadResult); rc CLY_ERR_CAPACITY
+        leaves the need in the result's value_bytes."""
+        nf = len(dev_files)
+        arr = (_abi.ClyFile * max(1, nf))()
+        for i, (ptr, ln, fid) in enumerate(dev_files):
+            arr[i].base, arr[i].len, arr[i].fid = ptr, ln, fid
+        r = _abi.ClyReadResult()
+        rc = self.lib.cly_read_device(self.ctx, arr, nf, d_pos, n, d_tuples, d_status, d_val_off, d_values,
+                                      values_cap, ctypes.byref(r), stream)
+        return rc, r
 
     def merge(self, files, live, data_file_size):
         """db.merge's rewrite loop (merge.go:90-143) on the device, host buffers

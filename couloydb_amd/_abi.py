@@ -94,6 +94,9 @@ GEN_SYMBOLS = ["cly_gen_record_size", "cly_gen_layout", "cly_gen_encode"]
 LOAD_SYMBOLS = ["cly_db_open", "cly_db_open_opts", "cly_db_open_multi", "cly_db_close", "cly_db_get", "cly_db_listmeta", "cly_db_hget",
                 "cly_db_lget", "cly_db_sget", "cly_db_value", "cly_index_key", "cly_db_count", "cly_db_entries",
                 "cly_load_prepare"]
+READ_SYMBOLS = ["cly_read_device", "cly_read"]
+# per-position statuses of cly_read* beyond the ReadLogRecord terminals (include/clyread.h)
+READ_REC, READ_NOFILE = 100, 101
 DB_NOT_FOUND, DB_EOF = 1, 2
 ERR_DIR, ERR_MERGE_FIN, ERR_KEY_EMPTY = -14, -15, -16
 IT_STRING, IT_LISTMETA, IT_HASH, IT_LIST, IT_SET, IT_EXPIRED = range(6)
@@ -116,6 +119,12 @@ class ClyLoadStats(ctypes.Structure):
                 ("sweep_files", ctypes.c_uint32), ("n_shards", ctypes.c_uint32), ("_pad2", ctypes.c_uint32),
                 ("tuple_slots", ctypes.c_uint64), ("order_ms", ctypes.c_double), ("order_rounds", ctypes.c_uint32),
                 ("_pad3", ctypes.c_uint32)]
+
+
+class ClyReadResult(ctypes.Structure):
+    _fields_ = [("n_rec", ctypes.c_uint64), ("n_eof", ctypes.c_uint64), ("n_crc", ctypes.c_uint64),
+                ("n_other", ctypes.c_uint64), ("n_nofile", ctypes.c_uint64), ("value_bytes", ctypes.c_uint64),
+                ("record_bytes", ctypes.c_uint64), ("read_ms", ctypes.c_double)]
 
 
 class ClyDbOptions(ctypes.Structure):
@@ -221,6 +230,15 @@ def load_scan_lib(name="libclyscan.so"):
                                ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
                                P(ctypes.c_uint64), ctypes.c_void_p, P(ClyAppendResult)]
     lib.cly_append.restype = ctypes.c_int
+    if hasattr(lib, "cly_read"):                  # (libraries of earlier builds, tools/build_r3_lib.sh)
+        lib.cly_read_device.argtypes = [ctypes.c_void_p, P(ClyFile), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_uint64, P(ClyReadResult), ctypes.c_void_p]
+        lib.cly_read_device.restype = ctypes.c_int
+        lib.cly_read.argtypes = [ctypes.c_void_p, P(ClyFile), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_uint64, P(ClyReadResult)]
+        lib.cly_read.restype = ctypes.c_int
     lib.cly_strerror.argtypes = [ctypes.c_int]
     lib.cly_strerror.restype = ctypes.c_char_p
     lib.cly_build_info.argtypes = []

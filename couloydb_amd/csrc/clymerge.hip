@@ -52,7 +52,8 @@ enum { MS_FB, MS_TOT, MS_PLAN, MS_BSUM, MS_ENT, MS_FSTART, MS_FLEN, MS_CP, MS_PR
        MS_PK, MS_PKC,
        MS_A0 = 16, MS_AN = MS_A0 + 16,            // cly_append_device's buffers
        MS_I0 = MS_AN, MS_IN = MS_I0 + 32,         // cly_index_device's buffers (clyindex.hip)
-       MS_N = MS_IN };
+       MS_R0 = MS_IN, MS_RN = MS_R0 + 24,         // cly_read_device's / cly_read's buffers (clyread.hip)
+       MS_N = MS_RN };
 struct MergeScratch { void* p[MS_N]; size_t cap[MS_N]; };
 extern "C" void cly_merge_scratch_free(void* v) {
     MergeScratch* m = (MergeScratch*)v;
@@ -86,6 +87,12 @@ static hipError_t scratch(cly_ctx* ctx, int slot, size_t bytes, T** out) {
 extern "C" hipError_t cly_ix_scratch_internal(cly_ctx* ctx, int k, size_t bytes, void** out) {
     if (k < 0 || MS_I0 + k >= MS_IN) return hipErrorInvalidValue;
     return scratch(ctx, MS_I0 + k, bytes, out);
+}
+
+// for clyread.hip: slot k of the read's range
+extern "C" hipError_t cly_rd_scratch_internal(cly_ctx* ctx, int k, size_t bytes, void** out) {
+    if (k < 0 || MS_R0 + k >= MS_RN) return hipErrorInvalidValue;
+    return scratch(ctx, MS_R0 + k, bytes, out);
 }
 
 #define M_NT 256

@@ -1,0 +1,455 @@
+"""Batched ReadLogRecord by position (include/clyread.h): cly_read_device and
+cly_read against the oracle's clyo_read_log_record, one call per position, and
+the file bytes for the values.  The CPU tests check the boundary (exports,
+struct layout); the GPU tests run on both builds of the library."""
+import ctypes
+import glob
+import os
+import random
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from couloydb_amd import DataFile, ErrInvalidCRC, ScanError, Scanner, TUPLE_DTYPE, _abi
+from oracle import cly_oracle as co
+
+from .gpu_util import mg, mixed_corpus
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+LIBS = ["libclyscan.so", "libclyscan_small.so"]
+REC, NOFILE = 100, 101
+
+
+# ---------------------------------------------------------------------------
+# CPU
+def declared_functions(header):
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"^[A-Za-z_][\w \*]*?\b(cly_\w+)\s*\(", src, flags=re.M)))
+
+
+@pytest.mark.parametrize("lib", LIBS)
+def test_library_exports_read_symbols(lib):
+    path = _abi.lib_path(lib)
+    assert os.path.exists(path), "build the libraries first (__graft_entry__.build())"
+    h = ctypes.CDLL(path)
+    names = declared_functions("clyread.h")
+    for n in names:
+        assert hasattr(h, n), "%s missing from %s" % (n, lib)
+    assert names == sorted(_abi.READ_SYMBOLS)
+    assert (_abi.READ_REC, _abi.READ_NOFILE) == (REC, NOFILE) and co.REC == _abi.READ_REC
+
+
+def test_read_result_layout():
+    src = r'''
+    #include <stdio.h>
+    #include <stddef.h>
+    #include "clyread.h"
+    int main(void){ printf("%zu %zu %d %d\n", sizeof(cly_read_result), offsetof(cly_read_result, read_ms),
+      CLY_READ_REC, CLY_READ_NOFILE); return 0; }
+    '''
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "t")
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    assert out[0] == ctypes.sizeof(_abi.ClyReadResult) == 64
+    assert out[1] == _abi.ClyReadResult.read_ms.offset == 56
+    assert out[2:] == [_abi.READ_REC, _abi.READ_NOFILE]
+
+
+# ---------------------------------------------------------------------------
+# GPU helpers
+gpu = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", params=LIBS)
+def scanner(request):
+    s = Scanner(0, lib=request.param)
+    yield s
+    s.close()
+
+
+def as_u8(data):
+    return data if isinstance(data, np.ndarray) else np.frombuffer(data, np.uint8).copy()
+
+
+def make_pos(pairs):
+    pos = np.zeros(len(pairs), _abi.POS_DTYPE)
+    if len(pairs):
+        pos["fid"] = [p[0] for p in pairs]
+        pos["offset"] = [p[1] for p in pairs]
+    return pos
+
+
+_expect_cache = {}
+
+
+def oracle_read(filemap, pos, shift=0):
+    """One clyo_read_log_record per position -> (status, tuples, val_off,
+    values); filemap = {fid: uint8 array}.  shift: the device file's offset of
+    the host array's byte 0 (the 4-GiB test)."""
+    n = len(pos)
+    L = co.lib()
+    st = np.zeros(n, np.int32)
+    tup = np.zeros(n, TUPLE_DTYPE)
+    voff = np.zeros(n + 1, np.uint64)
+    vals = []
+    one = np.zeros(1, co.TUPLE_DTYPE)
+    for i in range(n):
+        fid, off = int(pos[i]["fid"]), int(pos[i]["offset"])
+        tup[i]["fid"], tup[i]["offset"] = fid, off
+        F = filemap.get(fid)
+        nv = 0
+        if F is None:
+            st[i] = NOFILE
+        elif off < 0:
+            st[i] = _abi.ERR_OFFSET
+        elif off < shift:
+            st[i] = _abi.END_ZERO             # (the 4-GiB test's zero bytes below the host array)
+        else:
+            one[:] = 0
+            h = off - shift
+            st[i] = L.clyo_read_log_record(F.ctypes.data if F.size else None, F.size, h, one.ctypes.data)
+            if st[i] == REC:
+                one["fid"] = fid
+                one["offset"] = off
+                tup[i] = one.view(TUPLE_DTYPE)[0]
+                nv = int(one["value_size"][0])
+                e = h + int(one["size"][0])
+                vals.append(F[e - nv:e])
+        voff[i + 1] = voff[i] + np.uint64(nv)
+    values = np.concatenate(vals) if vals else np.zeros(0, np.uint8)
+    return st, tup, voff, values
+
+
+def tallies(st):
+    return dict(n_rec=int((st == REC).sum()), n_eof=int(((st >= 0) & (st <= 2)).sum()),
+                n_crc=int((st == _abi.ERR_CRC).sum()), n_nofile=int((st == NOFILE).sum()),
+                n_other=int(((st < -1)).sum()))
+
+
+class DevRun:
+    pass
+
+
+def run_device(sc, files, pos, values="fit", tuples=True, slack=4096, cap=None, dev=None):
+    """cly_read_device over host inputs uploaded with torch.  files = [(uint8
+    array, fid)] or dev = [(ptr, len, fid)]; the value buffer is pre-filled
+    with 0xA5 and `slack` bytes larger than `cap`."""
+    import torch
+    keep = []
+    if dev is None:
+        dev = []
+        for a, fid in files:
+            t = torch.from_numpy(a).cuda() if a.size else torch.zeros(0, dtype=torch.uint8, device="cuda")
+            keep.append(t)
+            dev.append((t.data_ptr() if a.size else None, int(a.size), fid))
+    n = len(pos)
+    d_pos = torch.from_numpy(pos.view(np.uint8).reshape(-1).copy()).cuda() if n else None
+    d_tup = torch.full((max(1, n) * 48,), 0x5A, dtype=torch.uint8, device="cuda") if tuples else None
+    d_st = torch.full((max(1, n),), -77, dtype=torch.int32, device="cuda")
+    d_vo = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
+    r = DevRun()
+    if values is None:
+        d_val, cap = None, 0
+    else:
+        assert cap is not None
+        d_val = torch.full((cap + slack,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    r.rc, r.rr = sc.read_device(dev, d_pos.data_ptr() if n else None, n, d_tup.data_ptr() if tuples else None,
+                                d_st.data_ptr(), d_vo.data_ptr(), d_val.data_ptr() if d_val is not None else None, cap)
+    torch.cuda.synchronize()
+    r.status = d_st.cpu().numpy()[:n]
+    r.tuples = d_tup.cpu().numpy().view(TUPLE_DTYPE)[:n] if tuples else None
+    r.val_off = d_vo.cpu().numpy().view(np.uint64)
+    r.values = d_val.cpu().numpy() if d_val is not None else None
+    del keep
+    return r
+
+
+def check(r, exp, label="", tuples=True, values=True):
+    st, tup, voff, vals = exp
+    bad = np.nonzero(r.status != st)[0]
+    assert bad.size == 0, "%s status at %d: gpu=%d oracle=%d (tuple offset %d)" % (
+        label, bad[0], r.status[bad[0]], st[bad[0]], tup[bad[0]]["offset"])
+    if tuples:
+        g = r.tuples.view(np.uint8).reshape(-1, 48)
+        o = tup.view(np.uint8).reshape(-1, 48)
+        bad = np.nonzero((g != o).any(axis=1))[0]
+        assert bad.size == 0, "%s tuple %d: gpu=%s oracle=%s" % (label, bad[0], r.tuples[bad[0]], tup[bad[0]])
+    assert (r.val_off == voff).all(), "%s val_off" % label
+    t = tallies(st)
+    for k, v in t.items():
+        assert getattr(r.rr, k) == v, "%s rr.%s=%d oracle=%d" % (label, k, getattr(r.rr, k), v)
+    assert r.rr.n_rec + r.rr.n_eof + r.rr.n_crc + r.rr.n_other + r.rr.n_nofile == len(st)
+    assert r.rr.value_bytes == int(voff[-1])
+    assert r.rr.record_bytes == int(tup["header_size"][st == REC].astype(np.uint64).sum() +
+                                    tup["key_size"][st == REC].astype(np.uint64).sum() +
+                                    tup["value_size"][st == REC].astype(np.uint64).sum())
+    if values:
+        nb = int(voff[-1])
+        assert (r.values[:nb] == vals).all(), "%s values" % label
+        assert (r.values[nb:] == 0xA5).all(), "%s bytes past value_bytes were written" % label
+
+
+def read_and_check(sc, files, pos, label=""):
+    exp = oracle_read({fid: a for a, fid in files}, pos)
+    r = run_device(sc, files, pos, cap=int(exp[2][-1]))
+    assert r.rc == 0, "%s rc=%d" % (label, r.rc)
+    check(r, exp, label)
+    return r, exp
+
+
+# ---------------------------------------------------------------------------
+# the file of the span-length tests: CRC spans (size - 4) of 5..130,
+# 4090..4102, 8186..8198, 65 540 and ~300 KiB.  encode_record's shortest span
+# is the 5 header bytes after the CRC (type, data type, three varints), so
+# 1..4 do not exist in this encoding; the every-byte-offset test reads the
+# headers that do not come from the writer.
+SPANS = list(range(5, 131)) + list(range(4090, 4103)) + list(range(8186, 8199)) + [65540, 300 * 1024 + 37]
+
+
+def record_with_span(span, k, rng):
+    key = b"" if span < 24 else mg.key_tx(mg.test_key(k), 0 if k % 3 else 1000 + k)
+    typ, dt, exp = (0, 0, 0) if span < 40 else (k % 2 * 3, k % 5, [0, 1 << 40, -1][k % 3])
+    for pad in range(3):           # (a value-length varint that grows a byte skips one span: pad the key)
+        for vs in range(max(0, span - len(key) - 20), span):
+            val = rng.randbytes(vs)
+            rec = mg.encode_record(key, val, typ, dt, exp)
+            if len(rec) - 4 == span:
+                return rec, (key, val, typ, dt, exp)
+        key += b"+"
+    raise AssertionError(span)
+
+
+def build_span_file():
+    if "span" in _expect_cache:
+        return _expect_cache["span"]
+    rng = random.Random(5)
+    b = bytearray()
+    recs = []                      # (offset, size, inputs) of every record, spacers included
+    for k, span in enumerate(SPANS):
+        if span < 10000:           # a spacer whose key length cycles 1..64: every start residue mod 64
+            sk = bytes([65 + k % 26]) * (k % 64 + 1)
+            sp = mg.encode_record(sk, b"", 0, 0, 0)
+            recs.append((len(b), len(sp), (sk, b"", 0, 0, 0)))
+            b += sp
+        rec, inp = record_with_span(span, k, rng)
+        recs.append((len(b), len(rec), inp))
+        b += rec
+    tomb = mg.encode_record(mg.key_tx(b"gone", 0), b"", mg.DELETED, 0, 0)
+    recs.append((len(b), len(tomb), (mg.key_tx(b"gone", 0), b"", mg.DELETED, 0, 0)))
+    b += tomb
+    assert len(b) < 2 << 20
+    assert len({o % 64 for o, _, _ in recs}) == 64
+    data = np.frombuffer(bytes(b), np.uint8).copy()
+    order = list(range(len(recs)))
+    random.Random(55).shuffle(order)
+    pairs = []
+    for j, k in enumerate(order):
+        pairs.append((3, recs[k][0]))
+        if j % 5 == 0:
+            pairs.append((3, recs[k][0]))
+    _expect_cache["span"] = (data, recs, make_pos(pairs))
+    return _expect_cache["span"]
+
+
+def rec_by_span(recs, span):
+    return [i for i, (o, s, _) in enumerate(recs) if s - 4 == span][0]
+
+
+# ---------------------------------------------------------------------------
+# GPU
+@gpu
+def test_golden_fixtures(scanner):
+    files, pairs = [], []
+    for fid, path in enumerate(sorted(glob.glob(os.path.join(GOLD, "*.cly")))):
+        a = np.fromfile(path, np.uint8) if os.path.getsize(path) else np.zeros(0, np.uint8)
+        files.append((a, fid))
+        t, st, end = co.scan_file(a, fid)
+        offs = {int(end)}
+        for r in t:
+            o, s = int(r["offset"]), int(r["size"])
+            offs |= {o, o + 1, o + s - 1}
+        ln = a.size
+        offs |= {ln - 6, ln - 5, ln - 4, ln, ln + 7}
+        pairs += [(fid, o) for o in sorted(offs) if o >= 0]
+    pairs.append((0, -5))
+    pairs.append((len(files) + 100, 0))
+    _, exp = read_and_check(scanner, files, make_pos(pairs), "golden")
+    assert (exp[0] == REC).sum() >= 1000 and {int(x) for x in exp[0]} >= {0, 1, 2, -1, -2, -3, -4, REC, NOFILE}
+
+
+@gpu
+def test_every_byte_offset(scanner):
+    rng = random.Random(9)
+    b = bytearray()
+    i = 0
+    while len(b) < 2048:
+        tx = 0 if i % 2 else rng.randrange(1, 1 << 40)
+        b += mg.encode_record(mg.key_tx(mg.test_key(i)[:rng.randrange(0, 10)], tx), rng.randbytes(rng.randrange(0, 40)),
+                              rng.choice([0, 1, 2]), rng.choice([0, 1, 4]), rng.choice([0, -1, 1 << 40]))
+        i += 1
+    a = np.frombuffer(bytes(b), np.uint8).copy()
+    pos = make_pos([(1, o) for o in range(a.size + 3)])
+    _, exp = read_and_check(scanner, [(a, 1)], pos, "every offset")
+    assert {int(x) for x in exp[0]} >= {_abi.END_EOF, _abi.END_TORN, _abi.ERR_CRC, _abi.ERR_TRUNC5, REC}
+
+
+@gpu
+def test_span_lengths_and_alignments(scanner):
+    data, recs, pos = build_span_file()
+    r, exp = read_and_check(scanner, [(data, 3)], pos, "spans")
+    assert (exp[0] == REC).all()
+
+
+@gpu
+def test_corruption(scanner):
+    import torch
+    data, recs, pos = build_span_file()
+    clean = oracle_read({3: data}, pos)
+    d = data.copy()
+    dev = torch.zeros(d.size, dtype=torch.uint8, device="cuda")
+    big = rec_by_span(recs, SPANS[-1])
+    bo = recs[big][0]
+    line = bo + 4096 + (-(dev.data_ptr() + bo + 4096)) % 4096        # a 4-KiB boundary of the source address
+    assert (dev.data_ptr() + line) % 4096 == 0 and bo + 4 < line < bo + recs[big][1]
+    hit = {rec_by_span(recs, 77): recs[rec_by_span(recs, 77)][0] + 4,                    # first byte after the CRC
+           rec_by_span(recs, 4097): sum(recs[rec_by_span(recs, 4097)][:2]) - 1,          # last value byte
+           big: line,
+           rec_by_span(recs, 65540): recs[rec_by_span(recs, 65540)][0] + 33333,
+           rec_by_span(recs, 10): recs[rec_by_span(recs, 10)][0] + 2}                    # the stored CRC itself
+    assert len(hit) == 5
+    for k, at in hit.items():
+        d[at] ^= 1 << (k % 8)
+    bad_offs = {recs[k][0] for k in hit}
+    pos2 = np.concatenate([pos, make_pos([(3, o) for o in sorted(bad_offs)])])           # duplicates of each for sure
+    clean2 = oracle_read({3: data}, pos2)
+    exp = oracle_read({3: d}, pos2)
+    is_bad = np.isin(pos2["offset"], sorted(bad_offs))
+    assert (exp[0][is_bad] == _abi.ERR_CRC).all() and (exp[0][~is_bad] == clean2[0][~is_bad]).all()
+    assert is_bad.sum() >= 10 and int(exp[2][-1]) < int(clean2[2][-1]) and len(clean[0]) == len(pos)
+    dev.copy_(torch.from_numpy(d))
+    r = run_device(scanner, None, pos2, cap=int(exp[2][-1]), dev=[(dev.data_ptr(), d.size, 3)])
+    assert r.rc == 0
+    check(r, exp, "corruption")
+
+
+@gpu
+def test_multiple_files(scanner):
+    fids = [0, 7, 4000000000]
+    files, pairs = [], []
+    for j, fid in enumerate(fids):
+        a = as_u8(mixed_corpus(40 + j, 256 * 1024))
+        files.append((a, fid))
+        t, st, end = co.scan_file(a, fid)
+        pairs += [(fid, int(o)) for o in t["offset"]] + [(fid, int(end)), (fid, a.size - 3)]
+    files.append((np.zeros(0, np.uint8), 9))
+    pairs += [(9, 0), (9, 5), (8, 0), (4000000001, 10)]
+    random.Random(7).shuffle(pairs)
+    pos = make_pos(pairs)
+    r, exp = read_and_check(scanner, files, pos, "multi")
+    assert r.status[pairs.index((9, 0))] == _abi.END_EOF and r.status[pairs.index((8, 0))] == NOFILE
+    dup = run_device(scanner, files + [(files[1][0], 7)], pos, values=None)
+    assert dup.rc == _abi.ERR_ARG
+
+
+@gpu
+def test_protocol(scanner):
+    data, recs, pos = build_span_file()
+    files = [(data, 3)]
+    pos = np.concatenate([pos[:60], make_pos([(3, data.size), (4, 0), (3, -1), (3, 1)])])
+    exp = oracle_read({3: data}, pos)
+    need = int(exp[2][-1])
+    assert need > 1 and min(tallies(exp[0]).values()) >= 1        # every counter of rr is exercised
+    # n == 0
+    r = run_device(scanner, files, make_pos([]), cap=0)
+    assert r.rc == 0 and r.val_off[0] == 0 and r.rr.n_rec == 0 and (r.values == 0xA5).all()
+    # nfiles == 0: every position is NOFILE
+    r = run_device(scanner, [], pos[:5], cap=0)
+    assert r.rc == 0 and (r.status == NOFILE).all() and r.rr.n_nofile == 5 and (r.val_off == 0).all()
+    # the verify-and-size pass
+    r = run_device(scanner, files, pos, values=None)
+    assert r.rc == 0
+    check(r, exp, "size pass", values=False)
+    # one byte short: everything but the values, which stay untouched
+    r = run_device(scanner, files, pos, cap=need - 1)
+    assert r.rc == _abi.ERR_CAPACITY and r.rr.value_bytes == need
+    check(r, exp, "capacity", values=False)
+    assert (r.values == 0xA5).all()
+    # no tuples wanted
+    r = run_device(scanner, files, pos, tuples=False, cap=need)
+    assert r.rc == 0
+    check(r, exp, "no tuples", tuples=False)
+    # argument errors
+    rr = _abi.ClyReadResult()
+    lib = scanner.lib
+    assert lib.cly_read_device(None, None, 0, None, 0, None, None, None, None, 0, ctypes.byref(rr), None) == _abi.ERR_ARG
+    assert lib.cly_read_device(scanner.ctx, None, 0, None, 0, None, None, None, None, 0, None, None) == _abi.ERR_ARG
+    assert lib.cly_read_device(scanner.ctx, None, 0, None, 3, None, 1 << 20, 1 << 20, None, 0, ctypes.byref(rr),
+                               None) == _abi.ERR_ARG
+
+
+@gpu
+def test_offsets_above_4gib(scanner):
+    import torch
+    with open(os.path.join(GOLD, "c1_shape.cly"), "rb") as f:
+        head = np.frombuffer(f.read(40 * 1024), np.uint8)
+    start = (1 << 32) - 1500
+    total = (1 << 32) + 64 * 1024
+    host = np.zeros(total - start, np.uint8)          # the device file from `start` on
+    host[:head.size] = head
+    t, st, end = co.scan_file(host, 0)
+    assert len(t) > 20 and any(int(r["offset"]) + start < (1 << 32) < int(r["offset"]) + start + int(r["size"]) for r in t)
+    dev = torch.zeros(total, dtype=torch.uint8, device="cuda")
+    dev[start:].copy_(torch.from_numpy(host))
+    pos = make_pos([(0, int(o) + start) for o in t["offset"]] + [(0, int(end) + start), (0, 0), (0, total - 5)])
+    exp = oracle_read({0: host}, pos, shift=start)
+    assert exp[0][len(pos) - 2] == _abi.END_ZERO       # offset 0: the zero bytes before `start`
+    r = run_device(scanner, None, pos, cap=int(exp[2][-1]), dev=[(dev.data_ptr(), total, 0)])
+    assert r.rc == 0
+    check(r, exp, "4 GiB")
+    assert int(exp[2][-1]) > 20 * 1024
+
+
+@gpu
+def test_host_entry_and_wrapper(scanner):
+    data, recs, pos = build_span_file()
+    exp = oracle_read({3: data}, pos)
+    other = [DataFile(as_u8(mixed_corpus(70 + j, 20000)), 10 + j) for j in range(2)]
+    res = scanner.read([other[0], DataFile(data, 3), other[1]], pos)      # the positions name 1 of 3 files
+    assert (res.status == exp[0]).all() and (res.val_off == exp[2]).all()
+    assert (res.tuples.view(np.uint8) == exp[1].view(np.uint8)).all()
+    assert res.values.size == int(exp[2][-1]) and (res.values == exp[3]).all()
+    sized = scanner.read([DataFile(data, 3)], pos, values=False)
+    assert sized.values is None and sized.result.value_bytes == int(exp[2][-1]) and (sized.status == exp[0]).all()
+    offs = {o: inp for o, _, inp in recs}
+    seen_tomb = False
+    for i in range(0, len(pos), 3):
+        key, val, typ, dt, e = offs[int(pos[i]["offset"])]
+        rec = res.record(i)
+        assert (rec.key, rec.value, rec.type, rec.data_type, rec.expiration) == (key, val, typ, dt, e)
+    ti = [i for i in range(len(pos)) if int(pos[i]["offset"]) == recs[-1][0]][0]
+    tomb = res.record(ti)
+    seen_tomb = res.status[ti] == REC and tomb.type == mg.DELETED and tomb.value == b""
+    assert seen_tomb
+    # the documented exceptions
+    d = data.copy()
+    d[recs[5][0] + recs[5][1] - 1] ^= 4
+    bad = scanner.read([DataFile(d, 3)], [(3, recs[5][0]), (3, d.size - 2), (44, 0), (3, recs[6][0])])
+    assert list(bad.status) == [_abi.ERR_CRC, _abi.END_EOF, NOFILE, REC]
+    with pytest.raises(ErrInvalidCRC):
+        bad.record(0)
+    with pytest.raises(EOFError):
+        bad.record(1)
+    with pytest.raises(KeyError):
+        bad.record(2)
+    assert bad.record(3).key == recs[6][2][0]
+    with pytest.raises(ScanError):
+        scanner.read([DataFile(d, 3)], [(3, -1)]).record(0)

@@ -38,10 +38,8 @@
 #include "scan_core.h"
 #include "ixkey.h"
 
-extern "C" hipStream_t cly_ctx_stream_internal(cly_ctx* c);
-extern "C" int64_t cly_ctx_now_internal(cly_ctx* c);
-extern "C" int cly_ctx_device_internal(cly_ctx* c);
-extern "C" hipError_t cly_ix_scratch_internal(cly_ctx* ctx, int k, size_t bytes, void** out);
+#define CLY_TAG "clyindex"
+#include "cly_internal.h"
 
 #define IX_NONE 0xFFFFFFFFFFFFFFFFull
 // record index of a hash-sorted entry: bit 31 carries "LogRecordDeleted" so that
@@ -524,9 +522,6 @@ k_ixgatherd(const uint64_t* __restrict__ hash, const uint32_t* __restrict__ sel,
 }
 
 // ---------------------------------------------------------------------------
-#define ICK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    fprintf(stderr, "clyindex: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = CLY_ERR_DEVICE; goto done; } } while (0)
-
 // The key hash keeps hbits = log2(n) + 24 bits (multiple of 8, 32..64):
 // expected colliding pairs n^2 / 2^(hbits+1) <= 2^-25 n stay ~0, and the radix
 // sort makes hbits/8 passes instead of 8.  Test hook: CLY_IX_HASH_MASK (hex)
@@ -557,11 +552,6 @@ static void ix_pk_bits(uint64_t n, int hbits, uint32_t& ib, uint32_t& hb) {
     if (h > hbits) h = hbits;
     hb = (uint32_t)h;
 }
-// The device buffer of the key hashes of the last cly_index_device call of
-// this context (n values: the records applied to an index; others undefined).
-extern "C" hipError_t cly_ix_hash_ptr_internal(cly_ctx* ctx, uint64_t n, void** out) {
-    return cly_ix_scratch_internal(ctx, 13, sizeof(uint64_t) * n, out);
-}
 
 static unsigned ix_grid(uint64_t n) { const uint64_t b = (n + 255) / 256; return (unsigned)(b < 16384 ? (b ? b : 1) : 16384); }
 
@@ -570,7 +560,7 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
                                 cly_index_result* ir, void* stream_v) {
     if (!ctx || !ir || nfiles < 0 || (nfiles && (!files || !file_first || !res))) return CLY_ERR_ARG;
     memset(ir, 0, sizeof(*ir));
-    const int64_t now_ns = cly_ctx_now_internal(ctx);
+    const int64_t now_ns = cly_now_ns(ctx);
     uint64_t n = 0;
     for (int i = 0; i < nfiles; i++) {
         if (res[i].status < 0) return res[i].status;           // loadIndex returns the scan's error
@@ -579,8 +569,8 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
     }
     if (n == 0) return CLY_OK;
     if (n >= (1ull << 31) || !d_state) return CLY_ERR_ARG;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = stream_v ? (hipStream_t)stream_v : cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     int rc = CLY_OK;
     uint64_t* h_fb = (uint64_t*)malloc(sizeof(uint64_t) * (2 * (size_t)nfiles + 2));
     for (int i = 0; i < nfiles; i++) { h_fb[i] = file_first[i]; h_fb[nfiles + 1 + i] = (uint64_t)files[i].base; }
@@ -607,73 +597,73 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
     uint64_t* d_pk = nullptr;
     const uint64_t* d_first = nullptr;
     const uint64_t* d_bases = nullptr;
-    ICK(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));     // (timing only)
-    ICK(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
-    ICK(cly_ix_scratch_internal(ctx, 0, sizeof(uint64_t) * (2 * (size_t)nfiles + 2), (void**)&d_fb));
+    CLY_CKG(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));     // (timing only)
+    CLY_CKG(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
+    CLY_CKG(cly_scratch(ctx, IS_FB, sizeof(uint64_t) * (2 * (size_t)nfiles + 2), &d_fb));
     d_first = d_fb;
     d_bases = d_fb + nfiles + 1;
-    ICK(cly_ix_scratch_internal(ctx, 1, sizeof(IxTot), (void**)&d_tot));
-    ICK(cly_ix_scratch_internal(ctx, 2, sizeof(unsigned long long), (void**)&d_nsel));
-    ICK(cly_ix_scratch_internal(ctx, 3, n, (void**)&d_cls));
-    ICK(cly_ix_scratch_internal(ctx, 4, n, (void**)&d_flag));
-    ICK(cly_ix_scratch_internal(ctx, 5, n + 4, (void**)&d_coll));     // (k_ixwin sets bytes by word atomics)
-    ICK(cly_ix_scratch_internal(ctx, 6, n, (void**)&d_del));
-    ICK(cly_ix_scratch_internal(ctx, 7, n, (void**)&d_apflag));
-    ICK(cly_ix_scratch_internal(ctx, 9, sizeof(uint4) * n, (void**)&d_ksig));
-    ICK(cly_ix_scratch_internal(ctx, 10, sizeof(uint64_t) * n, (void**)&d_txkey));
-    ICK(cly_ix_scratch_internal(ctx, 11, sizeof(uint64_t) * n, (void**)&d_k2));
-    ICK(cly_ix_scratch_internal(ctx, 12, sizeof(uint64_t) * n, (void**)&d_order));
-    ICK(cly_ix_scratch_internal(ctx, 13, sizeof(uint64_t) * n, (void**)&d_hash));
-    ICK(cly_ix_scratch_internal(ctx, 14, sizeof(uint32_t) * n, (void**)&d_sel));
-    ICK(cly_ix_scratch_internal(ctx, 15, sizeof(uint32_t) * n, (void**)&d_sidx));
-    ICK(cly_ix_scratch_internal(ctx, 16, sizeof(TxNext) * n, (void**)&d_rev));
-    ICK(cly_ix_scratch_internal(ctx, 17, sizeof(TxNext) * n, (void**)&d_nxt));
-    ICK(cly_ix_scratch_internal(ctx, 18, sizeof(GMax) * n, (void**)&d_g));
-    ICK(cly_ix_scratch_internal(ctx, 19, sizeof(GMax) * n, (void**)&d_g2));
-    ICK(cly_ix_scratch_internal(ctx, 21, sizeof(uint64_t) * n, (void**)&d_pk));
+    CLY_CKG(cly_scratch(ctx, IS_TOT, sizeof(IxTot), &d_tot));
+    CLY_CKG(cly_scratch(ctx, IS_NSEL, sizeof(unsigned long long), &d_nsel));
+    CLY_CKG(cly_scratch(ctx, IS_CLS, n, &d_cls));
+    CLY_CKG(cly_scratch(ctx, IS_FLAG, n, &d_flag));
+    CLY_CKG(cly_scratch(ctx, IS_COLL, n + 4, &d_coll));     // (k_ixwin sets bytes by word atomics)
+    CLY_CKG(cly_scratch(ctx, IS_DEL, n, &d_del));
+    CLY_CKG(cly_scratch(ctx, IS_APFLAG, n, &d_apflag));
+    CLY_CKG(cly_scratch(ctx, IS_KSIG, sizeof(uint4) * n, &d_ksig));
+    CLY_CKG(cly_scratch(ctx, IS_TXKEY, sizeof(uint64_t) * n, &d_txkey));
+    CLY_CKG(cly_scratch(ctx, IS_K2, sizeof(uint64_t) * n, &d_k2));
+    CLY_CKG(cly_scratch(ctx, IS_ORDER, sizeof(uint64_t) * n, &d_order));
+    CLY_CKG(cly_scratch(ctx, IS_HASH, sizeof(uint64_t) * n, &d_hash));
+    CLY_CKG(cly_scratch(ctx, IS_SEL, sizeof(uint32_t) * n, &d_sel));
+    CLY_CKG(cly_scratch(ctx, IS_SIDX, sizeof(uint32_t) * n, &d_sidx));
+    CLY_CKG(cly_scratch(ctx, IS_REV, sizeof(TxNext) * n, &d_rev));
+    CLY_CKG(cly_scratch(ctx, IS_NXT, sizeof(TxNext) * n, &d_nxt));
+    CLY_CKG(cly_scratch(ctx, IS_G, sizeof(GMax) * n, &d_g));
+    CLY_CKG(cly_scratch(ctx, IS_G2, sizeof(GMax) * n, &d_g2));
+    CLY_CKG(cly_scratch(ctx, IS_PK, sizeof(uint64_t) * n, &d_pk));
     // temp storage: the largest of the select / sort / scan needs
-    ICK(rocprim::select(nullptr, need, cnt, d_flag, d_sel, d_nsel, (size_t)n, st));
+    CLY_CKG(rocprim::select(nullptr, need, cnt, d_flag, d_sel, d_nsel, (size_t)n, st));
     tmp_bytes = need;
-    ICK(rocprim::radix_sort_pairs(nullptr, need, d_k2, d_txkey, d_sel, d_sidx, (size_t)n, 0u, 64u, st));
+    CLY_CKG(rocprim::radix_sort_pairs(nullptr, need, d_k2, d_txkey, d_sel, d_sidx, (size_t)n, 0u, 64u, st));
     if (need > tmp_bytes) tmp_bytes = need;
-    ICK(rocprim::radix_sort_keys(nullptr, need, d_k2, d_txkey, (size_t)n, 0u, 64u, st));
+    CLY_CKG(rocprim::radix_sort_keys(nullptr, need, d_k2, d_txkey, (size_t)n, 0u, 64u, st));
     if (need > tmp_bytes) tmp_bytes = need;
-    ICK(rocprim::inclusive_scan(nullptr, need, d_rev, d_nxt, (size_t)n, TxNextOp(), st));
+    CLY_CKG(rocprim::inclusive_scan(nullptr, need, d_rev, d_nxt, (size_t)n, TxNextOp(), st));
     if (need > tmp_bytes) tmp_bytes = need;
-    ICK(rocprim::inclusive_scan(nullptr, need, d_g, d_g2, (size_t)n, GMaxOp(), st));
+    CLY_CKG(rocprim::inclusive_scan(nullptr, need, d_g, d_g2, (size_t)n, GMaxOp(), st));
     if (need > tmp_bytes) tmp_bytes = need;
-    ICK(cly_ix_scratch_internal(ctx, 20, tmp_bytes, &d_tmp));
-    ICK(hipMemcpyAsync(d_fb, h_fb, sizeof(uint64_t) * (2 * (size_t)nfiles + 1), hipMemcpyHostToDevice, st));
-    ICK(hipMemsetAsync(d_tot, 0, sizeof(IxTot), st));
-    ICK(hipMemsetAsync(d_coll, 0, n + 4, st));
-    ICK(hipEventRecord(e0, st));
+    CLY_CKG(cly_scratch(ctx, IS_TMP, tmp_bytes, &d_tmp));
+    CLY_CKG(hipMemcpyAsync(d_fb, h_fb, sizeof(uint64_t) * (2 * (size_t)nfiles + 1), hipMemcpyHostToDevice, st));
+    CLY_CKG(hipMemsetAsync(d_tot, 0, sizeof(IxTot), st));
+    CLY_CKG(hipMemsetAsync(d_coll, 0, n + 4, st));
+    CLY_CKG(hipEventRecord(e0, st));
     hm = ix_hash_mask(n, hbits);
     ix_pk_bits(n, hbits, ib, hb);
     k_ixclass<<<grid, 256, 0, st>>>(d_tuples, n, d_cls, d_state, d_flag, d_tot, d_first, d_bases, nfiles, d_hash,
                                     d_apflag, d_del, d_ksig, d_pk, hm, ib, hb, now_ns);
-    ICK(hipMemcpyAsync(&h_tot, d_tot, sizeof(IxTot), hipMemcpyDeviceToHost, st));
-    ICK(hipStreamSynchronize(st));
+    CLY_CKG(hipMemcpyAsync(&h_tot, d_tot, sizeof(IxTot), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     // ---- transactions: tx records sorted by txId (stable: scan order within a txId)
     if (h_tot.n_tx) {
         size_t tb = tmp_bytes;
-        ICK(rocprim::select(d_tmp, tb, cnt, d_flag, d_sel, d_nsel, (size_t)n, st));
-        ICK(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(h_nsel), hipMemcpyDeviceToHost, st));
-        ICK(hipStreamSynchronize(st));
+        CLY_CKG(rocprim::select(d_tmp, tb, cnt, d_flag, d_sel, d_nsel, (size_t)n, st));
+        CLY_CKG(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(h_nsel), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         m = h_nsel;
     }
     if (m) {
         // (tx data records' application orders: k_ixtx; the others stay IX_NONE)
-        ICK(hipMemsetAsync(d_order, 0xff, sizeof(uint64_t) * n, st));
+        CLY_CKG(hipMemsetAsync(d_order, 0xff, sizeof(uint64_t) * n, st));
         k_ixgathertx<<<ix_grid(m), 256, 0, st>>>(d_tuples, d_sel, m, d_k2);
         {
             size_t tb = tmp_bytes;
             // sorted txIds into d_txkey (free after the gather; d_hash holds k_ixclass's hashes)
-            ICK(rocprim::radix_sort_pairs(d_tmp, tb, d_k2, d_txkey, d_sel, d_sidx, (size_t)m, 0u, 64u, st));
+            CLY_CKG(rocprim::radix_sort_pairs(d_tmp, tb, d_k2, d_txkey, d_sel, d_sidx, (size_t)m, 0u, 64u, st));
         }
         k_ixtxin<<<ix_grid(m), 256, 0, st>>>(d_txkey, d_sidx, d_cls, m, d_rev);
         {
             size_t tb = tmp_bytes;
-            ICK(rocprim::inclusive_scan(d_tmp, tb, d_rev, d_nxt, (size_t)m, TxNextOp(), st));
+            CLY_CKG(rocprim::inclusive_scan(d_tmp, tb, d_rev, d_nxt, (size_t)m, TxNextOp(), st));
         }
         k_ixtx<<<ix_grid(m), 256, 0, st>>>(d_sidx, d_cls, m, d_nxt, d_order, d_state);
     }
@@ -685,9 +675,9 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         m2 = n;                                                 // every record applied: no select
     } else {
         size_t tb = tmp_bytes;
-        ICK(rocprim::select(d_tmp, tb, cnt, d_apflag, d_sel, d_nsel, (size_t)n, st));
-        ICK(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(h_nsel), hipMemcpyDeviceToHost, st));
-        ICK(hipStreamSynchronize(st));
+        CLY_CKG(rocprim::select(d_tmp, tb, cnt, d_apflag, d_sel, d_nsel, (size_t)n, st));
+        CLY_CKG(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(h_nsel), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         m2 = h_nsel;
     }
     if (m2) {
@@ -698,19 +688,19 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         {
             // sorted keys into d_txkey (free after the tx phase)
             size_t tb = tmp_bytes;
-            ICK(rocprim::radix_sort_keys(d_tmp, tb, ident ? d_pk : d_k2, d_txkey, (size_t)m2, ib + 1u, ib + 1u + hb,
-                                         st));
+            CLY_CKG(rocprim::radix_sort_keys(d_tmp, tb, ident ? d_pk : d_k2, d_txkey, (size_t)m2, ib + 1u, ib + 1u + hb,
+                                             st));
         }
         if (m) {                    // tx records: application order != scan order, arg-max per group
             k_ixgin<<<ix_grid(m2), 256, 0, st>>>(d_txkey, ib, d_cls, d_order, m2, d_g);
             size_t tb = tmp_bytes;
-            ICK(rocprim::inclusive_scan(d_tmp, tb, d_g, d_g2, (size_t)m2, GMaxOp(), st));
+            CLY_CKG(rocprim::inclusive_scan(d_tmp, tb, d_g, d_g2, (size_t)m2, GMaxOp(), st));
         }
         // (d_sel is free after the sort: the collided groups' heads)
         k_ixwin<<<ix_grid(m2), 256, 0, st>>>(d_txkey, ib, m ? d_g2 : nullptr, m2, d_tuples, d_first, d_bases,
                                              nfiles, d_ksig, d_state, d_coll, d_sel, d_tot);
-        ICK(hipMemcpyAsync(&h_tot, d_tot, sizeof(IxTot), hipMemcpyDeviceToHost, st));
-        ICK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemcpyAsync(&h_tot, d_tot, sizeof(IxTot), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         if (h_tot.n_chead)
             k_ixcoll<<<(unsigned)((h_tot.n_chead + 255) / 256), 256, 0, st>>>(
                 d_txkey, ib, d_cls, d_order, m2, d_tuples, d_first, d_bases, nfiles, d_ksig, d_hash, d_del, d_state,
@@ -718,10 +708,10 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         k_ixwinfix<<<ix_grid(n), 256, 0, st>>>(d_tuples, n, d_first, d_bases, nfiles, d_del, d_state);
     }
     k_ixcount<<<ix_grid(n) < 1024 ? ix_grid(n) : 1024, 256, 0, st>>>(d_state, d_apflag, n, d_tot);
-    ICK(hipGetLastError());
-    ICK(hipEventRecord(e1, st));
-    ICK(hipMemcpyAsync(&h_tot, d_tot, sizeof(IxTot), hipMemcpyDeviceToHost, st));
-    ICK(hipStreamSynchronize(st));
+    CLY_CKG(hipGetLastError());
+    CLY_CKG(hipEventRecord(e1, st));
+    CLY_CKG(hipMemcpyAsync(&h_tot, d_tot, sizeof(IxTot), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     if (h_tot.bad) { rc = CLY_ERR_VARINT; goto done; }
     ir->n_live = h_tot.n_live;
     ir->n_applied = h_tot.n_applied;
@@ -731,7 +721,7 @@ extern "C" int cly_index_device(cly_ctx* ctx, const cly_file* files, int nfiles,
     ir->n_collisions = h_tot.n_coll;
     {
         float ms = 0;
-        ICK(hipEventElapsedTime(&ms, e0, e1));
+        CLY_CKG(hipEventElapsedTime(&ms, e0, e1));
         ir->index_ms = ms;
     }
 done:
@@ -750,8 +740,8 @@ extern "C" int cly_index(cly_ctx* ctx, const cly_file* files, int nfiles, uint8_
     if (!ctx || !ir || !n_out || nfiles < 0 || (nfiles && !files)) return CLY_ERR_ARG;
     memset(ir, 0, sizeof(*ir));
     *n_out = 0;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = ctx->stream;
     int rc = CLY_OK;
     uint64_t total = 0;
     for (int i = 0; i < nfiles; i++) {
@@ -765,32 +755,32 @@ extern "C" int cly_index(cly_ctx* ctx, const cly_file* files, int nfiles, uint8_
     uint8_t *d_bytes = nullptr, *d_state = nullptr;
     cly_tuple* d_tup = nullptr;
     uint64_t need = 0, cap_t = 0, T = 0, off = 0;
-    ICK(hipMalloc((void**)&d_bytes, total + 4096));
+    CLY_CKG(hipMalloc((void**)&d_bytes, total + 4096));
     for (int i = 0; i < nfiles; i++) {
         df[i] = files[i];
         df[i].base = d_bytes + off;
-        if (files[i].len) ICK(hipMemcpyAsync(d_bytes + off, files[i].base, files[i].len, hipMemcpyHostToDevice, st));
+        if (files[i].len) CLY_CKG(hipMemcpyAsync(d_bytes + off, files[i].base, files[i].len, hipMemcpyHostToDevice, st));
         off += (files[i].len + 4095) & ~4095ULL;
     }
     cap_t = cly_scan_capacity(files, nfiles) + 16;
-    ICK(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * cap_t));
+    CLY_CKG(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * cap_t));
     rc = cly_scan_device(ctx, df, nfiles, d_tup, cap_t, first, res, &need, nullptr, nullptr);
     if (rc != CLY_OK) goto done;
     for (int i = 0; i < nfiles; i++) {
         if (res[i].status < 0) { rc = res[i].status; goto done; }
         if (first[i] != T && res[i].n_records)
-            ICK(hipMemcpyAsync(d_tup + T, d_tup + first[i], sizeof(cly_tuple) * res[i].n_records,
-                               hipMemcpyDeviceToDevice, st));
+            CLY_CKG(hipMemcpyAsync(d_tup + T, d_tup + first[i], sizeof(cly_tuple) * res[i].n_records,
+                                   hipMemcpyDeviceToDevice, st));
         first[i] = T;
         T += res[i].n_records;
     }
     *n_out = T;
     if (T > cap) { rc = CLY_ERR_CAPACITY; goto done; }
-    ICK(hipMalloc((void**)&d_state, T + 1));
+    CLY_CKG(hipMalloc((void**)&d_state, T + 1));
     rc = cly_index_device(ctx, df, nfiles, d_tup, first, res, d_state, ir, nullptr);
     if (rc != CLY_OK) goto done;
-    if (T) ICK(hipMemcpyAsync(state, d_state, T, hipMemcpyDeviceToHost, st));
-    ICK(hipStreamSynchronize(st));
+    if (T) CLY_CKG(hipMemcpyAsync(state, d_state, T, hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
 done:
     hipStreamSynchronize(st);
     hipFree(d_bytes); hipFree(d_tup); hipFree(d_state);

@@ -49,16 +49,9 @@
 #include "scan_core.h"
 #include "ixkey.h"
 
-extern "C" hipStream_t cly_ctx_stream_internal(cly_ctx* c);
-extern "C" int cly_ctx_device_internal(cly_ctx* c);
-extern "C" uint64_t cly_ix_hash_mask_internal(uint64_t n);
-extern "C" hipError_t cly_ix_hash_ptr_internal(cly_ctx* ctx, uint64_t n, void** out);
-extern "C" int cly_order_keys_internal(hipStream_t st, const cly_tuple* d_tup, uint64_t n, const uint8_t* d_state,
-                                       uint32_t dt, const uint64_t* first, const uint64_t* bases, int nf,
-                                       uint32_t** d_ord_out, uint64_t* m_out, uint32_t* rounds_out);
-extern "C" int cly_scan_device_alloc_internal(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple** d_out,
-                                              uint64_t* cap, uint64_t* file_first, cly_file_result* res,
-                                              uint64_t* needed);
+#define CLY_TAG "clyload"
+#include "cly_internal.h"
+
 #define LOAD_PIECE (64ull << 20)
 #define LOAD_STAGE (8ull << 20)            // page-locked staging buffer (two per copy thread)
 #define LOAD_THREADS_MAX 16
@@ -532,7 +525,7 @@ static int copy_to_host(cly_ctx* ctx, const std::vector<D2H>& parts, int t0, int
             pieces.push_back({(uint8_t*)x.dst + a, (const uint8_t*)x.src + a, std::min<uint64_t>(LOAD_PIECE, x.len - a)});
     std::atomic<size_t> next(0);
     std::atomic<int> err(0);
-    const int dev = cly_ctx_device_internal(ctx);
+    const int dev = ctx->device;
     std::unique_lock<std::mutex> lk(g_stage_mu, std::defer_lock);     // (lock = false: the caller holds it)
     if (lock) lk.lock();
     // (threads t0 .. t0+nt-1, each with its own two staging buffers)
@@ -618,7 +611,7 @@ static std::vector<uint8_t> tombstone(const uint8_t* key, uint64_t klen) {
 static int flat_device(cly_ctx* ctx, cly_db* db, const cly_file* df, int nall, const cly_tuple* d_tup,
                        const std::vector<uint64_t>& first, const std::vector<cly_file_result>& res, uint8_t* d_state,
                        const cly_pos* d_hpos, uint64_t need, cly_index_result& ir, int nb, cly_load_stats& s) {
-    hipStream_t strm = cly_ctx_stream_internal(ctx);
+    hipStream_t strm = ctx->stream;
     if (nall) {
         const int rc = cly_index_device(ctx, df, nall, d_tup, first.data(), res.data(), d_state, &ir, nullptr);
         if (rc != CLY_OK) return rc;
@@ -635,7 +628,7 @@ static int flat_device(cly_ctx* ctx, cly_db* db, const cly_file* df, int nall, c
     uint64_t geo[4 * FLAT_SHARDS], tot = 0;
     const unsigned grid = (unsigned)std::min<uint64_t>((need + 255) / 256, 8192);
     std::vector<D2H> parts = {{db->state.data(), d_state, need}};
-    DCK(cly_ix_hash_ptr_internal(ctx, need, (void**)&d_hash));
+    DCK(cly_scratch(ctx, IS_HASH, sizeof(uint64_t) * need, &d_hash));
     DCK(hipMalloc((void**)&d_cnt, sizeof(cnt) + sizeof(geo)));
     d_geo = (uint64_t*)(d_cnt + 2 * FLAT_SHARDS);
     DCK(hipMemsetAsync(d_cnt, 0, sizeof(cnt), strm));
@@ -756,7 +749,7 @@ extern "C" int cly_db_open_multi(cly_ctx* const* ctxs, int nctx, const char* dir
     cly_db* db = new cly_db();
     int rc = list_files(dir, db->files, db->fid_ix);
     const int nf = (int)db->files.size();
-    const int dev0 = cly_ctx_device_internal(ctx);
+    const int dev0 = ctx->device;
     bool has_hint = false;
     int nall = 0;                                // hint (file 0 when present) + data files
     cly_tuple* d_tup = nullptr;                  // every tuple, in file order, on the first context's device
@@ -769,7 +762,7 @@ extern "C" int cly_db_open_multi(cly_ctx* const* ctxs, int nctx, const char* dir
     std::vector<uint64_t> first;
     std::vector<LoadShard> sh(nctx);
     uint64_t need = 0;
-    hipStream_t strm = cly_ctx_stream_internal(ctx);
+    hipStream_t strm = ctx->stream;
     double t1, t2 = 0, t3, t4, t5;
     cly_index_result ir;
     if (rc != CLY_OK) goto done;
@@ -798,7 +791,7 @@ extern "C" int cly_db_open_multi(cly_ctx* const* ctxs, int nctx, const char* dir
         int f = 0;
         for (int k = 0; k < nctx; k++) {
             sh[k].ctx = ctxs[k];
-            sh[k].dev = cly_ctx_device_internal(ctxs[k]);
+            sh[k].dev = ctxs[k]->device;
             sh[k].f0 = f;
             const uint64_t target = tot / (uint64_t)nctx * (uint64_t)(k + 1) + (k + 1 == nctx ? tot : 0);
             while (f < nall && (f == 0 || acc + (hf[f].len + 4096) / 2 <= target)) acc += hf[f++].len + 4096;

@@ -42,58 +42,8 @@
 
 #include "scan_core.h"
 
-extern "C" hipStream_t cly_ctx_stream_internal(cly_ctx* c);
-extern "C" int cly_ctx_device_internal(cly_ctx* c);
-extern "C" void** cly_ctx_merge_slot_internal(cly_ctx* c);
-
-// Scratch buffers of the merge, kept in the context and grown on demand
-// (plain hipMalloc: no allocation inside a timed merge once warm).
-enum { MS_FB, MS_TOT, MS_PLAN, MS_BSUM, MS_ENT, MS_FSTART, MS_FLEN, MS_CP, MS_PRE, MS_BMAP, MS_HSZ, MS_KEYS,
-       MS_PK, MS_PKC,
-       MS_A0 = 16, MS_AN = MS_A0 + 16,            // cly_append_device's buffers
-       MS_I0 = MS_AN, MS_IN = MS_I0 + 32,         // cly_index_device's buffers (clyindex.hip)
-       MS_R0 = MS_IN, MS_RN = MS_R0 + 24,         // cly_read_device's / cly_read's buffers (clyread.hip)
-       MS_N = MS_RN };
-struct MergeScratch { void* p[MS_N]; size_t cap[MS_N]; };
-extern "C" void cly_merge_scratch_free(void* v) {
-    MergeScratch* m = (MergeScratch*)v;
-    if (!m) return;
-    for (int i = 0; i < MS_N; i++) if (m->p[i]) hipFree(m->p[i]);
-    free(m);
-}
-template <class T>
-static hipError_t scratch(cly_ctx* ctx, int slot, size_t bytes, T** out) {
-    void** s = cly_ctx_merge_slot_internal(ctx);
-    if (!*s) *s = calloc(1, sizeof(MergeScratch));
-    MergeScratch* m = (MergeScratch*)*s;
-    if (bytes == 0) bytes = 16;
-    if (m->cap[slot] < bytes) {
-        if (m->p[slot]) { hipError_t e = hipFree(m->p[slot]); if (e != hipSuccess) return e; }
-        m->p[slot] = nullptr;
-        m->cap[slot] = 0;
-        // 1/8 slack against regrowth; CLY_MERGE_EXACT=1 allocates exactly (the
-        // regression test of the round-1 k_mplan fault runs both)
-        static const bool exact = getenv("CLY_MERGE_EXACT") != nullptr;
-        const size_t want = exact ? bytes : bytes + bytes / 8;
-        hipError_t e = hipMalloc(&m->p[slot], want);
-        if (e != hipSuccess) return e;
-        m->cap[slot] = want;
-    }
-    *out = (T*)m->p[slot];
-    return hipSuccess;
-}
-
-// for clyindex.hip: slot k of the index's range
-extern "C" hipError_t cly_ix_scratch_internal(cly_ctx* ctx, int k, size_t bytes, void** out) {
-    if (k < 0 || MS_I0 + k >= MS_IN) return hipErrorInvalidValue;
-    return scratch(ctx, MS_I0 + k, bytes, out);
-}
-
-// for clyread.hip: slot k of the read's range
-extern "C" hipError_t cly_rd_scratch_internal(cly_ctx* ctx, int k, size_t bytes, void** out) {
-    if (k < 0 || MS_R0 + k >= MS_RN) return hipErrorInvalidValue;
-    return scratch(ctx, MS_R0 + k, bytes, out);
-}
+#define CLY_TAG "clymerge"
+#include "cly_internal.h"
 
 #define M_NT 256
 #define M_IT 16
@@ -1007,8 +957,6 @@ static int merge_debug() {
     if (e_ == hipSuccess) e_ = hipGetLastError(); \
     fprintf(stderr, "clymerge: %s -> %s\n", name, hipGetErrorString(e_)); \
     if (e_ != hipSuccess) { rc = CLY_ERR_DEVICE; goto done; } } } while (0)
-#define MCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    fprintf(stderr, "clymerge: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = CLY_ERR_DEVICE; goto done; } } while (0)
 
 extern "C" int cly_merge_device(cly_ctx* ctx, const cly_file* files, int nfiles, const cly_tuple* d_tuples,
                                 const uint64_t* file_first, const cly_file_result* res, const uint8_t* d_live,
@@ -1028,8 +976,8 @@ extern "C" int cly_merge_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         T += res[i].n_records;
     }
     if (T >= (1ull << 32)) return CLY_ERR_ARG;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = stream_v ? (hipStream_t)stream_v : cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     int rc = CLY_OK;
     uint64_t* h_fb = (uint64_t*)malloc(sizeof(uint64_t) * (2 * (size_t)nfiles + 2));
     uint64_t *d_fb = nullptr, *d_plan = nullptr, *d_fstart = nullptr, *d_flen = nullptr, *d_pk = nullptr, *d_pkc = nullptr;
@@ -1043,21 +991,21 @@ extern "C" int cly_merge_device(cly_ctx* ctx, const cly_file* files, int nfiles,
     MTot h_tot;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const uint64_t nblk = T / M_BLK + 1;
-    MCK(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));     // (timing only)
-    MCK(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
+    CLY_CKG(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));     // (timing only)
+    CLY_CKG(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
     for (int i = 0; i < nfiles; i++) h_fb[i] = file_first[i];
     h_fb[nfiles] = T;
     for (int i = 0; i < nfiles; i++) h_fb[nfiles + 1 + i] = (uint64_t)files[i].base;
-    MCK(scratch(ctx, MS_FB, sizeof(uint64_t) * (2 * (size_t)nfiles + 2), &d_fb));
-    MCK(hipMemcpyAsync(d_fb, h_fb, sizeof(uint64_t) * (2 * (size_t)nfiles + 1), hipMemcpyHostToDevice, st));
-    MCK(scratch(ctx, MS_TOT, sizeof(MTot), &d_tot));
-    MCK(hipMemsetAsync(d_tot, 0, sizeof(MTot), st));
-    MCK(scratch(ctx, MS_PLAN, sizeof(uint64_t) * (T + 1), &d_plan));
-    MCK(scratch(ctx, MS_BSUM, sizeof(MSum) * nblk, &d_bsum));
-    MCK(scratch(ctx, MS_ENT, sizeof(MEnt) * (T + 1), &d_ent));
-    MCK(scratch(ctx, MS_PK, sizeof(uint64_t) * (T + 1), &d_pk));
-    MCK(scratch(ctx, MS_PKC, sizeof(uint64_t) * (T + 1), &d_pkc));
-    MCK(hipEventRecord(e0, st));
+    CLY_CKG(cly_scratch(ctx, MS_FB, sizeof(uint64_t) * (2 * (size_t)nfiles + 2), &d_fb));
+    CLY_CKG(hipMemcpyAsync(d_fb, h_fb, sizeof(uint64_t) * (2 * (size_t)nfiles + 1), hipMemcpyHostToDevice, st));
+    CLY_CKG(cly_scratch(ctx, MS_TOT, sizeof(MTot), &d_tot));
+    CLY_CKG(hipMemsetAsync(d_tot, 0, sizeof(MTot), st));
+    CLY_CKG(cly_scratch(ctx, MS_PLAN, sizeof(uint64_t) * (T + 1), &d_plan));
+    CLY_CKG(cly_scratch(ctx, MS_BSUM, sizeof(MSum) * nblk, &d_bsum));
+    CLY_CKG(cly_scratch(ctx, MS_ENT, sizeof(MEnt) * (T + 1), &d_ent));
+    CLY_CKG(cly_scratch(ctx, MS_PK, sizeof(uint64_t) * (T + 1), &d_pk));
+    CLY_CKG(cly_scratch(ctx, MS_PKC, sizeof(uint64_t) * (T + 1), &d_pkc));
+    CLY_CKG(hipEventRecord(e0, st));
     if (T) {
         k_mplan<<<(unsigned)nblk, M_NT, 0, st>>>(d_tuples, T, d_live, d_fb, d_fb + nfiles + 1, nfiles, d_plan, d_pk, d_bsum,
                                                   data_file_size, d_tot);
@@ -1067,8 +1015,8 @@ extern "C" int cly_merge_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         k_mcompact<<<(unsigned)nblk, M_NT, 0, st>>>(d_plan, d_pk, T, d_bsum, d_ent, d_pkc);
         MDBG(st, "k_mcompact");
     }
-    MCK(hipMemcpyAsync(&h_tot, d_tot, sizeof(MTot), hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    CLY_CKG(hipMemcpyAsync(&h_tot, d_tot, sizeof(MTot), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     if (h_tot.bad & 1) { rc = CLY_ERR_VARINT; goto done; }
     if (h_tot.bad & 2) { rc = CLY_ERR_ARG; goto done; }
     mres->n_live = h_tot.nl;
@@ -1078,35 +1026,35 @@ extern "C" int cly_merge_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         uint64_t fcap64 = 2 * h_tot.bytes / data_file_size + 4;
         if (fcap64 > h_tot.nl + 2) fcap64 = h_tot.nl + 2;
         const uint32_t fcap = (uint32_t)fcap64;
-        MCK(scratch(ctx, MS_FSTART, sizeof(uint64_t) * (fcap + 1), &d_fstart));
-        MCK(scratch(ctx, MS_FLEN, sizeof(uint64_t) * (fcap + 1), &d_flen));
+        CLY_CKG(cly_scratch(ctx, MS_FSTART, sizeof(uint64_t) * (fcap + 1), &d_fstart));
+        CLY_CKG(cly_scratch(ctx, MS_FLEN, sizeof(uint64_t) * (fcap + 1), &d_flen));
         k_mrot<<<1, M_ROT, 0, st>>>(d_ent, d_tot, data_file_size, fcap, d_fstart, d_flen);
         MDBG(st, "k_mrot");
-        MCK(hipMemcpyAsync(&h_tot, d_tot, sizeof(MTot), hipMemcpyDeviceToHost, st));
-        MCK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemcpyAsync(&h_tot, d_tot, sizeof(MTot), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         mres->n_out_files = h_tot.n_out;
         if (h_tot.n_out >= fcap) { rc = CLY_ERR_DEVICE; goto done; }   // cannot happen (bound above)
         const uint64_t nl = h_tot.nl;
         const uint64_t lblk = nl / M_BLK + 1;
         const uint64_t nblocks = (uint64_t)h_tot.n_out * (stride / M_CB);
         if (lblk > nblk) { rc = CLY_ERR_DEVICE; goto done; }    // cannot happen: nl <= T
-        MCK(scratch(ctx, MS_CP, sizeof(MCopy) * nl, &d_cp));
-        MCK(scratch(ctx, MS_PRE, (size_t)M_PRE * nl, &d_pre));
-        MCK(scratch(ctx, MS_BMAP, sizeof(uint32_t) * (nblocks + 1), &d_bmap));
-        MCK(scratch(ctx, MS_HSZ, sizeof(uint32_t) * nl, &d_hsz));
+        CLY_CKG(cly_scratch(ctx, MS_CP, sizeof(MCopy) * nl, &d_cp));
+        CLY_CKG(cly_scratch(ctx, MS_PRE, (size_t)M_PRE * nl, &d_pre));
+        CLY_CKG(cly_scratch(ctx, MS_BMAP, sizeof(uint32_t) * (nblocks + 1), &d_bmap));
+        CLY_CKG(cly_scratch(ctx, MS_HSZ, sizeof(uint32_t) * nl, &d_hsz));
         k_mplace<<<(unsigned)lblk, M_NT, 0, st>>>(d_ent, d_pkc, d_tuples, d_plan, d_fb, d_fb + nfiles + 1, nfiles, d_fstart,
                                                    d_tot, stride, d_cp, d_pre, d_bmap, d_hsz, d_bsum);
         MDBG(st, "k_mplace");
         k_msums<<<1, M_NT, 0, st>>>(d_bsum, lblk, &d_tot->hint_bytes, nullptr);
-        MCK(hipMemcpyAsync(&h_tot, d_tot, sizeof(MTot), hipMemcpyDeviceToHost, st));
-        MCK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemcpyAsync(&h_tot, d_tot, sizeof(MTot), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         mres->hint_bytes = h_tot.hint_bytes;
         mres->n_reencoded = h_tot.n_re;
         if (h_tot.n_out > out_max_files || !d_out || h_tot.hint_bytes > hint_cap || !d_hint) {
             rc = CLY_ERR_CAPACITY;
             goto done;
         }
-        MCK(scratch(ctx, MS_KEYS, sizeof(uint4) * nl, &d_keys));
+        CLY_CKG(cly_scratch(ctx, MS_KEYS, sizeof(uint4) * nl, &d_keys));
         const uint64_t wgs = (nblocks + MC_W - 1) / MC_W;
         unsigned grid = wgs < 16384 ? (unsigned)wgs : 16384u;
         k_mcopy<M_CMAX, M_PRE, true><<<grid, 64 * MC_W, 0, st>>>(d_cp, d_pre, d_bmap, d_fstart, d_flen, stride, nblocks,
@@ -1115,16 +1063,16 @@ extern "C" int cly_merge_device(cly_ctx* ctx, const cly_file* files, int nfiles,
         k_mhint<<<(unsigned)lblk, M_NT, 0, st>>>(d_ent, d_cp, d_tuples, d_keys, d_hsz, d_bsum, d_tot, stride, d_hint,
                                                   hint_cap);
         MDBG(st, "k_mhint");
-        MCK(hipGetLastError());
-        if (out_file_len) MCK(hipMemcpyAsync(out_file_len, d_flen, sizeof(uint64_t) * h_tot.n_out,
-                                             hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipGetLastError());
+        if (out_file_len) CLY_CKG(hipMemcpyAsync(out_file_len, d_flen, sizeof(uint64_t) * h_tot.n_out,
+                                                 hipMemcpyDeviceToHost, st));
     }
 timing:
-    MCK(hipEventRecord(e1, st));
-    MCK(hipEventSynchronize(e1));
+    CLY_CKG(hipEventRecord(e1, st));
+    CLY_CKG(hipEventSynchronize(e1));
     {
         float ms = 0;
-        MCK(hipEventElapsedTime(&ms, e0, e1));
+        CLY_CKG(hipEventElapsedTime(&ms, e0, e1));
         mres->merge_ms = ms;
     }
 done:
@@ -1143,8 +1091,8 @@ extern "C" int cly_merge(cly_ctx* ctx, const cly_file* files, int nfiles, const 
                          uint8_t* hint, uint64_t hint_cap, cly_merge_result* mres) {
     if (!ctx || !mres || nfiles < 0 || (nfiles && !files) || data_file_size == 0) return CLY_ERR_ARG;
     memset(mres, 0, sizeof(*mres));
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = ctx->stream;
     int rc = CLY_OK;
     const uint64_t stride = (data_file_size + M_CB - 1) / M_CB * M_CB;
     uint64_t total = 0;
@@ -1159,24 +1107,24 @@ extern "C" int cly_merge(cly_ctx* ctx, const cly_file* files, int nfiles, const 
     uint8_t *d_bytes = nullptr, *d_live = nullptr, *d_out = nullptr, *d_hint = nullptr;
     cly_tuple* d_tup = nullptr;
     uint64_t need = 0, cap = 0, T = 0;
-    MCK(hipMalloc((void**)&d_bytes, total + 4096));
+    CLY_CKG(hipMalloc((void**)&d_bytes, total + 4096));
     {
         uint64_t off = 0;
         for (int i = 0; i < nfiles; i++) {
             df[i] = files[i];
             df[i].base = d_bytes + off;
-            if (files[i].len) MCK(hipMemcpyAsync(d_bytes + off, files[i].base, files[i].len, hipMemcpyHostToDevice, st));
+            if (files[i].len) CLY_CKG(hipMemcpyAsync(d_bytes + off, files[i].base, files[i].len, hipMemcpyHostToDevice, st));
             off += (files[i].len + 4095) & ~4095ULL;
         }
     }
     cap = cly_scan_capacity(files, nfiles) + 16;
-    MCK(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * cap));
+    CLY_CKG(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * cap));
     rc = cly_scan_device(ctx, df, nfiles, d_tup, cap, first, res, &need, nullptr, nullptr);
     if (rc == CLY_ERR_CAPACITY) {
         hipFree(d_tup);
         d_tup = nullptr;
         cap = need + 16;
-        MCK(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * cap));
+        CLY_CKG(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * cap));
         rc = cly_scan_device(ctx, df, nfiles, d_tup, cap, first, res, &need, nullptr, nullptr);
     }
     if (rc != CLY_OK) goto done;
@@ -1189,24 +1137,24 @@ extern "C" int cly_merge(cly_ctx* ctx, const cly_file* files, int nfiles, const 
         uint64_t o = 0;
         for (int i = 0; i < nfiles; i++) {
             if (first[i] != o && res[i].n_records)
-                MCK(hipMemcpyAsync(d_tup + o, d_tup + first[i], sizeof(cly_tuple) * res[i].n_records,
-                                   hipMemcpyDeviceToDevice, st));
+                CLY_CKG(hipMemcpyAsync(d_tup + o, d_tup + first[i], sizeof(cly_tuple) * res[i].n_records,
+                                       hipMemcpyDeviceToDevice, st));
             first[i] = o;
             o += res[i].n_records;
         }
     }
     if (n_live_bytes != T || (T && !live)) { rc = CLY_ERR_ARG; goto done; }
-    MCK(hipMalloc((void**)&d_live, T + 1));
-    if (T) MCK(hipMemcpyAsync(d_live, live, T, hipMemcpyHostToDevice, st));
-    if (out_max_files) MCK(hipMalloc((void**)&d_out, stride * out_max_files));
-    if (hint_cap) MCK(hipMalloc((void**)&d_hint, hint_cap));
+    CLY_CKG(hipMalloc((void**)&d_live, T + 1));
+    if (T) CLY_CKG(hipMemcpyAsync(d_live, live, T, hipMemcpyHostToDevice, st));
+    if (out_max_files) CLY_CKG(hipMalloc((void**)&d_out, stride * out_max_files));
+    if (hint_cap) CLY_CKG(hipMalloc((void**)&d_hint, hint_cap));
     rc = cly_merge_device(ctx, df, nfiles, d_tup, first, res, d_live, data_file_size, d_out, out_max_files,
                           out_file_len, d_hint, hint_cap, mres, nullptr);
     if (rc != CLY_OK) goto done;
     for (uint32_t k = 0; k < mres->n_out_files; k++)
-        MCK(hipMemcpyAsync(out + k * stride, d_out + k * stride, out_file_len[k], hipMemcpyDeviceToHost, st));
-    if (mres->hint_bytes) MCK(hipMemcpyAsync(hint, d_hint, mres->hint_bytes, hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemcpyAsync(out + k * stride, d_out + k * stride, out_file_len[k], hipMemcpyDeviceToHost, st));
+    if (mres->hint_bytes) CLY_CKG(hipMemcpyAsync(hint, d_hint, mres->hint_bytes, hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
 done:
     hipStreamSynchronize(st);
     hipFree(d_bytes); hipFree(d_tup); hipFree(d_live); hipFree(d_out); hipFree(d_hint);
@@ -1246,18 +1194,18 @@ extern "C" int cly_hint_positions_device(cly_ctx* ctx, const uint8_t* d_hint_fil
     if (!ctx || (n && (!d_hint_file || !d_tuples || !d_pos))) return CLY_ERR_ARG;
     if (first_bad) *first_bad = n;
     if (!n) return CLY_OK;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = stream_v ? (hipStream_t)stream_v : cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     int rc = CLY_OK;
     unsigned long long* d_bad = nullptr;
     unsigned long long h_bad = ~0ull;
     const uint64_t blocks = (n + 255) / 256;
-    MCK(scratch(ctx, MS_TOT, sizeof(MTot), &d_bad));
-    MCK(hipMemcpyAsync(d_bad, &h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st));
+    CLY_CKG(cly_scratch(ctx, MS_TOT, sizeof(MTot), &d_bad));
+    CLY_CKG(hipMemcpyAsync(d_bad, &h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st));
     k_hintpos<<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, st>>>(d_hint_file, d_tuples, n, d_pos, d_bad);
-    MCK(hipGetLastError());
-    MCK(hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    CLY_CKG(hipGetLastError());
+    CLY_CKG(hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     if (h_bad < n) {
         if (first_bad) *first_bad = h_bad;
         rc = CLY_ERR_VARINT;
@@ -1270,8 +1218,8 @@ extern "C" int cly_hint_scan(cly_ctx* ctx, const cly_file* hint_file, cly_tuple*
                              uint64_t* n_out, cly_file_result* res) {
     if (!ctx || !hint_file || !res || !n_out) return CLY_ERR_ARG;
     *n_out = 0;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = ctx->stream;
     int rc = CLY_OK;
     uint8_t* d_bytes = nullptr;
     cly_tuple* d_tup = nullptr;
@@ -1279,15 +1227,15 @@ extern "C" int cly_hint_scan(cly_ctx* ctx, const cly_file* hint_file, cly_tuple*
     cly_file df = *hint_file;
     uint64_t first = 0, need = 0, nrec = 0, bad = 0;
     const uint64_t tcap = cly_scan_capacity(hint_file, 1) + 16;
-    MCK(hipMalloc((void**)&d_bytes, hint_file->len + 16));
-    if (hint_file->len) MCK(hipMemcpyAsync(d_bytes, hint_file->base, hint_file->len, hipMemcpyHostToDevice, st));
+    CLY_CKG(hipMalloc((void**)&d_bytes, hint_file->len + 16));
+    if (hint_file->len) CLY_CKG(hipMemcpyAsync(d_bytes, hint_file->base, hint_file->len, hipMemcpyHostToDevice, st));
     df.base = d_bytes;
-    MCK(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * tcap));
+    CLY_CKG(hipMalloc((void**)&d_tup, sizeof(cly_tuple) * tcap));
     rc = cly_scan_device(ctx, &df, 1, d_tup, tcap, &first, res, &need, nullptr, nullptr);
     if (rc != CLY_OK) goto done;
     nrec = res->n_records;
     if (nrec) {
-        MCK(hipMalloc((void**)&d_pos, sizeof(cly_pos) * nrec));
+        CLY_CKG(hipMalloc((void**)&d_pos, sizeof(cly_pos) * nrec));
         rc = cly_hint_positions_device(ctx, d_bytes, d_tup + first, nrec, d_pos, &bad, nullptr);
         if (rc == CLY_ERR_VARINT) nrec = bad;                  // the records before the panic
         else if (rc != CLY_OK) goto done;
@@ -1295,9 +1243,9 @@ extern "C" int cly_hint_scan(cly_ctx* ctx, const cly_file* hint_file, cly_tuple*
     *n_out = nrec;
     if (nrec > cap) { rc = CLY_ERR_CAPACITY; goto done; }
     if (nrec) {
-        MCK(hipMemcpyAsync(out, d_tup + first, sizeof(cly_tuple) * nrec, hipMemcpyDeviceToHost, st));
-        MCK(hipMemcpyAsync(pos, d_pos, sizeof(cly_pos) * nrec, hipMemcpyDeviceToHost, st));
-        MCK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemcpyAsync(out, d_tup + first, sizeof(cly_tuple) * nrec, hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipMemcpyAsync(pos, d_pos, sizeof(cly_pos) * nrec, hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
     }
 done:
     hipStreamSynchronize(st);
@@ -1456,8 +1404,8 @@ extern "C" int cly_append_device(cly_ctx* ctx, const cly_rec_in* d_recs, uint64_
     const uint64_t nt = n + (commit ? 1 : 0);
     if (nt == 0) { ar->n_out_files = 1; ar->final_fid = active_fid; ar->final_write_off = write_off; return CLY_OK; }
     if (2 * nt >= (1ull << 32)) return CLY_ERR_ARG;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = stream_v ? (hipStream_t)stream_v : cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     int rc = CLY_OK;
     uint64_t *d_sz = nullptr, *d_g = nullptr, *d_fstart = nullptr, *d_flen = nullptr, *h_flen = nullptr;
     uint32_t *d_nout = nullptr, *d_bmap = nullptr;
@@ -1471,24 +1419,24 @@ extern "C" int cly_append_device(cly_ctx* ctx, const cly_rec_in* d_recs, uint64_
     unsigned long long h_mx = 0, h_mn = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const unsigned grid = (unsigned)((nt + 255) / 256 < 16384 ? (nt + 255) / 256 : 16384);
-    MCK(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));     // (timing only)
-    MCK(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
-    MCK(scratch(ctx, MS_A0 + 0, sizeof(uint64_t) * nt, &d_sz));
-    MCK(scratch(ctx, MS_A0 + 1, sizeof(uint64_t) * nt, &d_g));
-    MCK(scratch(ctx, MS_A0 + 2, sizeof(uint32_t), &d_nout));
-    MCK(scratch(ctx, MS_A0 + 3, 2 * sizeof(unsigned long long), &d_mx));
-    MCK(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long), st));
-    MCK(hipMemsetAsync(d_mx + 1, 0xff, sizeof(unsigned long long), st));
-    MCK(rocprim::exclusive_scan(nullptr, tb, d_sz, d_g, (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
-    MCK(scratch(ctx, MS_A0 + 4, tb + 16, (char**)&d_tmp));
-    MCK(hipEventRecord(e0, st));
+    CLY_CKG(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));     // (timing only)
+    CLY_CKG(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
+    CLY_CKG(cly_scratch(ctx, AS_SZ, sizeof(uint64_t) * nt, &d_sz));
+    CLY_CKG(cly_scratch(ctx, AS_G, sizeof(uint64_t) * nt, &d_g));
+    CLY_CKG(cly_scratch(ctx, AS_NOUT, sizeof(uint32_t), &d_nout));
+    CLY_CKG(cly_scratch(ctx, AS_MX, 2 * sizeof(unsigned long long), &d_mx));
+    CLY_CKG(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long), st));
+    CLY_CKG(hipMemsetAsync(d_mx + 1, 0xff, sizeof(unsigned long long), st));
+    CLY_CKG(rocprim::exclusive_scan(nullptr, tb, d_sz, d_g, (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
+    CLY_CKG(cly_scratch(ctx, AS_TMP, tb + 16, (char**)&d_tmp));
+    CLY_CKG(hipEventRecord(e0, st));
     k_asize<<<grid, 256, 0, st>>>((const ARec*)d_recs, n, nt, tx_id, d_sz, d_mx);
-    MCK(rocprim::exclusive_scan(d_tmp, tb, d_sz, d_g, (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
-    MCK(hipMemcpyAsync(&last, d_sz + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    MCK(hipMemcpyAsync(&total, d_g + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    MCK(hipMemcpyAsync(&h_mx, d_mx, sizeof(h_mx), hipMemcpyDeviceToHost, st));
-    MCK(hipMemcpyAsync(&h_mn, d_mx + 1, sizeof(h_mn), hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    CLY_CKG(rocprim::exclusive_scan(d_tmp, tb, d_sz, d_g, (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
+    CLY_CKG(hipMemcpyAsync(&last, d_sz + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipMemcpyAsync(&total, d_g + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipMemcpyAsync(&h_mx, d_mx, sizeof(h_mx), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipMemcpyAsync(&h_mn, d_mx + 1, sizeof(h_mn), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     total += last;
     {
         // a region holds at most max(DataFileSize, one record, the active file's
@@ -1503,18 +1451,18 @@ extern "C" int cly_append_device(cly_ctx* ctx, const cly_rec_in* d_recs, uint64_
     // exists because the first could not take its first record)
     fcap = 2 * (total + write_off) / data_file_size + 4;
     if (fcap > nt + 2) fcap = nt + 2;
-    MCK(scratch(ctx, MS_A0 + 5, sizeof(uint64_t) * (fcap + 1), &d_fstart));
-    MCK(scratch(ctx, MS_A0 + 6, sizeof(uint64_t) * (fcap + 1), &d_flen));
+    CLY_CKG(cly_scratch(ctx, AS_FSTART, sizeof(uint64_t) * (fcap + 1), &d_fstart));
+    CLY_CKG(cly_scratch(ctx, AS_FLEN, sizeof(uint64_t) * (fcap + 1), &d_flen));
     k_arot<<<1, M_ROT, 0, st>>>(d_g, nt, total, data_file_size, write_off, (uint32_t)fcap, d_fstart, d_flen, d_nout);
-    MCK(hipMemcpyAsync(&h_nout, d_nout, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    CLY_CKG(hipMemcpyAsync(&h_nout, d_nout, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     ar->n_out_files = h_nout;
     ar->bytes = total;
     if (h_nout > out_max_files || !d_out || !d_pos) { rc = CLY_ERR_CAPACITY; goto done; }
     nblocks = (uint64_t)h_nout * (stride / M_CB);
-    MCK(scratch(ctx, MS_A0 + 7, sizeof(MCopy) * 2 * nt, &d_cp));
-    MCK(scratch(ctx, MS_A0 + 8, (size_t)A_PRE * 2 * nt, &d_pre));
-    MCK(scratch(ctx, MS_A0 + 9, sizeof(uint32_t) * (nblocks + 1), &d_bmap));
+    CLY_CKG(cly_scratch(ctx, AS_CP, sizeof(MCopy) * 2 * nt, &d_cp));
+    CLY_CKG(cly_scratch(ctx, AS_PRE, (size_t)A_PRE * 2 * nt, &d_pre));
+    CLY_CKG(cly_scratch(ctx, AS_BMAP, sizeof(uint32_t) * (nblocks + 1), &d_bmap));
     k_aplace<<<grid, 256, 0, st>>>((const ARec*)d_recs, n, nt, tx_id, d_g, d_fstart, d_nout, write_off, active_fid,
                                    stride, d_cp, d_pre, d_bmap, d_pos);
     {
@@ -1531,17 +1479,17 @@ extern "C" int cly_append_device(cly_ctx* ctx, const cly_rec_in* d_recs, uint64_
             k_mcopy<A_CMAX, A_PRE, false><<<cg, 64 * MC_W, 0, st>>>(d_cp, d_pre, d_bmap, d_fstart, d_flen, stride,
                                                                  nblocks, d_out, write_off, nullptr);
     }
-    MCK(hipGetLastError());
-    MCK(hipEventRecord(e1, st));
+    CLY_CKG(hipGetLastError());
+    CLY_CKG(hipEventRecord(e1, st));
     h_flen = (uint64_t*)malloc(sizeof(uint64_t) * h_nout);
-    MCK(hipMemcpyAsync(h_flen, d_flen, sizeof(uint64_t) * h_nout, hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    CLY_CKG(hipMemcpyAsync(h_flen, d_flen, sizeof(uint64_t) * h_nout, hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
     for (uint32_t k = 0; k < h_nout; k++) if (out_file_len) out_file_len[k] = h_flen[k];
     ar->final_fid = active_fid + h_nout - 1;
     ar->final_write_off = h_flen[h_nout - 1];
     {
         float ms = 0;
-        MCK(hipEventElapsedTime(&ms, e0, e1));
+        CLY_CKG(hipEventElapsedTime(&ms, e0, e1));
         ar->append_ms = ms;
     }
 done:
@@ -1561,8 +1509,8 @@ extern "C" int cly_append(cly_ctx* ctx, const cly_rec_in* recs, uint64_t n, int6
                           uint32_t out_max_files, uint64_t* out_file_len, cly_pos* pos, cly_append_result* ar) {
     if (!ctx || !ar || (n && !recs) || data_file_size == 0) return CLY_ERR_ARG;
     memset(ar, 0, sizeof(*ar));
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = ctx->stream;
     int rc = CLY_OK;
     uint64_t blob = 0;
     for (uint64_t i = 0; i < n; i++) blob += recs[i].key_len + recs[i].value_len;
@@ -1574,7 +1522,7 @@ extern "C" int cly_append(cly_ctx* ctx, const cly_rec_in* recs, uint64_t n, int6
     uint64_t o = 0;
     const uint64_t nt = n + (commit ? 1 : 0);
     cly_append_result q;
-    MCK(hipMalloc((void**)&d_blob, blob + 16));
+    CLY_CKG(hipMalloc((void**)&d_blob, blob + 16));
     for (uint64_t i = 0; i < n; i++) {
         h_recs[i] = recs[i];
         if (recs[i].key_len) memcpy(h_blob + o, recs[i].key, recs[i].key_len);
@@ -1584,27 +1532,27 @@ extern "C" int cly_append(cly_ctx* ctx, const cly_rec_in* recs, uint64_t n, int6
         h_recs[i].value = d_blob + o;
         o += recs[i].value_len;
     }
-    MCK(hipMalloc((void**)&d_recs, sizeof(cly_rec_in) * (n + 1)));
-    if (blob) MCK(hipMemcpyAsync(d_blob, h_blob, blob, hipMemcpyHostToDevice, st));
-    if (n) MCK(hipMemcpyAsync(d_recs, h_recs, sizeof(cly_rec_in) * n, hipMemcpyHostToDevice, st));
+    CLY_CKG(hipMalloc((void**)&d_recs, sizeof(cly_rec_in) * (n + 1)));
+    if (blob) CLY_CKG(hipMemcpyAsync(d_blob, h_blob, blob, hipMemcpyHostToDevice, st));
+    if (n) CLY_CKG(hipMemcpyAsync(d_recs, h_recs, sizeof(cly_rec_in) * n, hipMemcpyHostToDevice, st));
     rc = cly_append_device(ctx, d_recs, n, tx_id, commit, active_fid, write_off, data_file_size, nullptr, 0, nullptr,
                            nullptr, &q, nullptr);
     *ar = q;
     if (rc != CLY_OK && rc != CLY_ERR_CAPACITY) goto done;
     if (!out || !pos || q.n_out_files > out_max_files) { rc = CLY_ERR_CAPACITY; goto done; }
-    MCK(hipMalloc((void**)&d_out, q.out_stride * q.n_out_files));
-    MCK(hipMalloc((void**)&d_pos, sizeof(cly_pos) * (nt + 1)));
+    CLY_CKG(hipMalloc((void**)&d_out, q.out_stride * q.n_out_files));
+    CLY_CKG(hipMalloc((void**)&d_pos, sizeof(cly_pos) * (nt + 1)));
     rc = cly_append_device(ctx, d_recs, n, tx_id, commit, active_fid, write_off, data_file_size, d_out, q.n_out_files,
                            out_file_len, d_pos, ar, nullptr);
     if (rc != CLY_OK) goto done;
     for (uint32_t k = 0; k < ar->n_out_files; k++) {
         const uint64_t from = k == 0 ? write_off : 0;
         if (out_file_len[k] > from)
-            MCK(hipMemcpyAsync(out + k * ar->out_stride + from, d_out + k * ar->out_stride + from,
-                               out_file_len[k] - from, hipMemcpyDeviceToHost, st));
+            CLY_CKG(hipMemcpyAsync(out + k * ar->out_stride + from, d_out + k * ar->out_stride + from,
+                                   out_file_len[k] - from, hipMemcpyDeviceToHost, st));
     }
-    if (nt) MCK(hipMemcpyAsync(pos, d_pos, sizeof(cly_pos) * nt, hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    if (nt) CLY_CKG(hipMemcpyAsync(pos, d_pos, sizeof(cly_pos) * nt, hipMemcpyDeviceToHost, st));
+    CLY_CKG(hipStreamSynchronize(st));
 done:
     hipStreamSynchronize(st);
     hipFree(d_blob); hipFree(d_recs); hipFree(d_out); hipFree(d_pos);

@@ -30,8 +30,8 @@
 
 #include "scan_core.h"
 
-#define OCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    fprintf(stderr, "clyorder: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = CLY_ERR_DEVICE; goto done; } } while (0)
+#define CLY_TAG "clyorder"
+#include "cly_internal.h"
 
 // realKey of tuple ti: the file holding it (the last file whose first tuple
 // index is <= ti; empty files share their successor's first index and come
@@ -144,45 +144,45 @@ extern "C" int cly_order_keys_internal(hipStream_t st, const cly_tuple* d_tup, u
     unsigned long long h_cnt[3] = {0, 0, 0};
     uint64_t m = 0;
     uint32_t rounds = 0;
-    OCK(hipMalloc((void**)&d_cnt, sizeof(h_cnt)));
-    OCK(hipMalloc((void**)&d_fb, sizeof(uint64_t) * 2 * (nf ? nf : 1)));
-    OCK(hipMemcpyAsync(d_fb, bases, sizeof(uint64_t) * nf, hipMemcpyHostToDevice, st));
-    OCK(hipMemcpyAsync(d_fb + nf, first, sizeof(uint64_t) * nf, hipMemcpyHostToDevice, st));
-    OCK(hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), st));
-    OCK(hipMalloc((void**)&d_flag, n ? n : 1));
-    OCK(hipMalloc((void**)&d_sel, sizeof(uint32_t) * (n ? n : 1)));
-    OCK(rocprim::select(nullptr, need, rocprim::counting_iterator<uint32_t>(0), d_flag, d_sel,
-                                      d_cnt, (size_t)n, st));
+    CLY_CKG(hipMalloc((void**)&d_cnt, sizeof(h_cnt)));
+    CLY_CKG(hipMalloc((void**)&d_fb, sizeof(uint64_t) * 2 * (nf ? nf : 1)));
+    CLY_CKG(hipMemcpyAsync(d_fb, bases, sizeof(uint64_t) * nf, hipMemcpyHostToDevice, st));
+    CLY_CKG(hipMemcpyAsync(d_fb + nf, first, sizeof(uint64_t) * nf, hipMemcpyHostToDevice, st));
+    CLY_CKG(hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), st));
+    CLY_CKG(hipMalloc((void**)&d_flag, n ? n : 1));
+    CLY_CKG(hipMalloc((void**)&d_sel, sizeof(uint32_t) * (n ? n : 1)));
+    CLY_CKG(rocprim::select(nullptr, need, rocprim::counting_iterator<uint32_t>(0), d_flag, d_sel,
+                                          d_cnt, (size_t)n, st));
     tmp_bytes = need;
-    OCK(rocprim::radix_sort_pairs(nullptr, need, d_k1, d_ka, d_pa, d_pb, (size_t)n, 0u, 64u, st));
+    CLY_CKG(rocprim::radix_sort_pairs(nullptr, need, d_k1, d_ka, d_pa, d_pb, (size_t)n, 0u, 64u, st));
     if (need > tmp_bytes) tmp_bytes = need;
-    OCK(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 1));
+    CLY_CKG(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 1));
     if (n) {
         hipLaunchKernelGGL(k_ord_flag, dim3(ogrid(n)), dim3(256), 0, st, d_state, n, dt, d_flag);
-        OCK(rocprim::select(d_tmp, need = tmp_bytes, rocprim::counting_iterator<uint32_t>(0), d_flag,
-                                          d_sel, d_cnt, (size_t)n, st));
-        OCK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-        OCK(hipStreamSynchronize(st));
+        CLY_CKG(rocprim::select(d_tmp, need = tmp_bytes, rocprim::counting_iterator<uint32_t>(0), d_flag,
+                                              d_sel, d_cnt, (size_t)n, st));
+        CLY_CKG(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
     }
     m = h_cnt[0];
-    OCK(hipMalloc((void**)&d_ord, sizeof(uint32_t) * (m ? m : 1)));
+    CLY_CKG(hipMalloc((void**)&d_ord, sizeof(uint32_t) * (m ? m : 1)));
     if (m) {
-        OCK(hipMalloc((void**)&d_k0, sizeof(uint64_t) * m));
-        OCK(hipMalloc((void**)&d_k1, sizeof(uint64_t) * m));
-        OCK(hipMalloc((void**)&d_ka, sizeof(uint64_t) * m));
-        OCK(hipMalloc((void**)&d_pa, sizeof(uint32_t) * m));
-        OCK(hipMalloc((void**)&d_pb, sizeof(uint32_t) * m));
-        OCK(hipMalloc((void**)&d_tie, m));
+        CLY_CKG(hipMalloc((void**)&d_k0, sizeof(uint64_t) * m));
+        CLY_CKG(hipMalloc((void**)&d_k1, sizeof(uint64_t) * m));
+        CLY_CKG(hipMalloc((void**)&d_ka, sizeof(uint64_t) * m));
+        CLY_CKG(hipMalloc((void**)&d_pa, sizeof(uint32_t) * m));
+        CLY_CKG(hipMalloc((void**)&d_pb, sizeof(uint32_t) * m));
+        CLY_CKG(hipMalloc((void**)&d_tie, m));
         hipLaunchKernelGGL(k_ord_key0, dim3(ogrid(m)), dim3(256), 0, st, d_sel, m, d_tup, d_fb, nf, d_k0, d_k1, d_pa);
         // LSD: by k1 (stable), then by k0 (stable): the 128-bit order
-        OCK(rocprim::radix_sort_pairs(d_tmp, need = tmp_bytes, d_k1, d_ka, d_pa, d_pb, (size_t)m, 0u, 64u, st));
+        CLY_CKG(rocprim::radix_sort_pairs(d_tmp, need = tmp_bytes, d_k1, d_ka, d_pa, d_pb, (size_t)m, 0u, 64u, st));
         hipLaunchKernelGGL(k_ord_gather, dim3(ogrid(m)), dim3(256), 0, st, d_k0, d_pb, m, d_ka);
-        OCK(rocprim::radix_sort_pairs(d_tmp, need = tmp_bytes, d_ka, d_k0, d_pb, d_pa, (size_t)m, 0u, 64u, st));
+        CLY_CKG(rocprim::radix_sort_pairs(d_tmp, need = tmp_bytes, d_ka, d_k0, d_pb, d_pa, (size_t)m, 0u, 64u, st));
         hipLaunchKernelGGL(k_ord_fin0, dim3(ogrid(m)), dim3(256), 0, st, d_sel, d_pa, m, d_k0, d_k1, d_ord, d_tie,
                            d_cnt + 1);
-        OCK(hipGetLastError());
-        OCK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-        OCK(hipStreamSynchronize(st));
+        CLY_CKG(hipGetLastError());
+        CLY_CKG(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         // refinement rounds over the runs of equal 15-byte prefixes of long keys
         // (d_k0/d_k1/d_ka/d_pa/d_pb/d_sel/d_flag reused as round scratch)
         for (uint32_t off = 15; h_cnt[1]; off += 7) {
@@ -190,50 +190,50 @@ extern "C" int cly_order_keys_internal(hipStream_t st, const cly_tuple* d_tup, u
             uint8_t* d_inrun = d_flag;
             uint32_t* d_P = d_sel;
             hipLaunchKernelGGL(k_ord_inrun, dim3(ogrid(m)), dim3(256), 0, st, d_tie, m, d_inrun);
-            OCK(hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), st));
-            OCK(rocprim::select(d_tmp, need = tmp_bytes, rocprim::counting_iterator<uint32_t>(0),
-                                              d_inrun, d_P, d_cnt, (size_t)m, st));
-            OCK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-            OCK(hipStreamSynchronize(st));
+            CLY_CKG(hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), st));
+            CLY_CKG(rocprim::select(d_tmp, need = tmp_bytes, rocprim::counting_iterator<uint32_t>(0),
+                                                  d_inrun, d_P, d_cnt, (size_t)m, st));
+            CLY_CKG(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+            CLY_CKG(hipStreamSynchronize(st));
             const uint64_t np = h_cnt[0];
             uint64_t* d_key = d_k0;
             uint64_t* d_keys = d_k1;
             uint32_t* d_val = d_pa;
             uint32_t* d_vals = d_pb;
-            if (!d_aux) OCK(hipMalloc((void**)&d_aux, m + 1));
-            if (!d_vb) OCK(hipMalloc((void**)&d_vb, sizeof(uint32_t) * (m + 1)));
+            if (!d_aux) CLY_CKG(hipMalloc((void**)&d_aux, m + 1));
+            if (!d_vb) CLY_CKG(hipMalloc((void**)&d_vb, sizeof(uint32_t) * (m + 1)));
             hipLaunchKernelGGL(k_ord_keyr, dim3(ogrid(np)), dim3(256), 0, st, d_P, np, d_ord, d_tie, d_tup, d_fb, nf,
                                off, d_key, d_val, d_aux);
             // segment begins: the run starts among the members (+ np at the end)
-            OCK(rocprim::select(d_tmp, need = tmp_bytes, rocprim::counting_iterator<uint32_t>(0),
-                                              d_aux, d_vb, d_cnt + 2, (size_t)np, st));
-            OCK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-            OCK(hipStreamSynchronize(st));
+            CLY_CKG(rocprim::select(d_tmp, need = tmp_bytes, rocprim::counting_iterator<uint32_t>(0),
+                                                  d_aux, d_vb, d_cnt + 2, (size_t)np, st));
+            CLY_CKG(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+            CLY_CKG(hipStreamSynchronize(st));
             const uint64_t nseg = h_cnt[2];
             const uint32_t np32 = (uint32_t)np;
-            OCK(hipMemcpyAsync(d_vb + nseg, &np32, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            CLY_CKG(hipMemcpyAsync(d_vb + nseg, &np32, sizeof(uint32_t), hipMemcpyHostToDevice, st));
             size_t sneed = 0;
-            OCK(rocprim::segmented_radix_sort_pairs(nullptr, sneed, d_key, d_keys, d_val, d_vals, (unsigned)np,
-                                                        (unsigned)nseg, d_vb, d_vb + 1, 0u, 64u, st));
+            CLY_CKG(rocprim::segmented_radix_sort_pairs(nullptr, sneed, d_key, d_keys, d_val, d_vals, (unsigned)np,
+                                                            (unsigned)nseg, d_vb, d_vb + 1, 0u, 64u, st));
             if (sneed > tmp_bytes) {
-                OCK(hipStreamSynchronize(st));
+                CLY_CKG(hipStreamSynchronize(st));
                 hipFree(d_tmp);
                 d_tmp = nullptr;
                 tmp_bytes = sneed;
-                OCK(hipMalloc(&d_tmp, tmp_bytes));
+                CLY_CKG(hipMalloc(&d_tmp, tmp_bytes));
             }
-            OCK(rocprim::segmented_radix_sort_pairs(d_tmp, sneed, d_key, d_keys, d_val, d_vals, (unsigned)np,
-                                                        (unsigned)nseg, d_vb, d_vb + 1, 0u, 64u, st));
-            OCK(hipMemsetAsync(d_cnt + 1, 0, sizeof(unsigned long long), st));
+            CLY_CKG(rocprim::segmented_radix_sort_pairs(d_tmp, sneed, d_key, d_keys, d_val, d_vals, (unsigned)np,
+                                                            (unsigned)nseg, d_vb, d_vb + 1, 0u, 64u, st));
+            CLY_CKG(hipMemsetAsync(d_cnt + 1, 0, sizeof(unsigned long long), st));
             hipLaunchKernelGGL(k_ord_scatter, dim3(ogrid(np)), dim3(256), 0, st, d_P, np, d_keys, d_vals, d_aux,
                                d_ord, d_tie, d_cnt + 1);
-            OCK(hipGetLastError());
-            OCK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-            OCK(hipStreamSynchronize(st));
+            CLY_CKG(hipGetLastError());
+            CLY_CKG(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+            CLY_CKG(hipStreamSynchronize(st));
             if (off > (1u << 31)) { rc = CLY_ERR_DEVICE; goto done; }     // (never: keys are < 4 GiB)
         }
     }
-    OCK(hipStreamSynchronize(st));
+    CLY_CKG(hipStreamSynchronize(st));
     *d_ord_out = d_ord;
     d_ord = nullptr;
     *m_out = m;

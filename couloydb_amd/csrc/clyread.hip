@@ -40,22 +40,14 @@
 #include "../../include/clyread.h"
 #include "scan_core.h"
 
-extern "C" hipStream_t cly_ctx_stream_internal(cly_ctx* c);
-extern "C" int cly_ctx_device_internal(cly_ctx* c);
-extern "C" hipError_t cly_rd_scratch_internal(cly_ctx* ctx, int k, size_t bytes, void** out);
-
-#define RCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    fprintf(stderr, "clyread: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = CLY_ERR_DEVICE; goto done; } } while (0)
+#define CLY_TAG "clyread"
+#include "cly_internal.h"
 
 #define RD_NT 256                 // threads per workgroup (4 waves)
 #define RD_IT 8                   // 64-piece groups a wave of k_rd_crc / k_rd_gather takes in turn
 #define RD_SAFE_FIRST 1u          // the span's first 64-B line lies wholly inside the file
 #define RD_SAFE_LAST 2u           // the span's last 64-B line lies wholly inside the file
 #define RD_MAX_FILE_LEN ((1ull << 47) - 1)
-
-// scratch slots (cly_rd_scratch_internal)
-enum { RS_TAB, RS_FILES, RS_SPAN, RS_CNT, RS_POFS, RS_MULTI, RS_TOT, RS_SLOT, RS_TMP,
-       RS_H_BYTES, RS_H_POS, RS_H_TUP, RS_H_STATUS, RS_H_VOFF, RS_H_VAL };
 
 struct RdFile { uint64_t base, len; uint32_t fid, _pad; };     // fid-sorted device copy of cly_file
 struct RdSpan {                  // per position, 32 B (meaningful while its status is CLY_READ_REC)
@@ -424,74 +416,74 @@ static int read_impl(cly_ctx* ctx, const std::vector<RdFile>& sorted, const cly_
     RdTot tot;
     uint64_t P = 0;
     memset(rr, 0, sizeof(*rr));
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
     if (n == 0) {
-        RCK(hipMemsetAsync(d_val_off, 0, sizeof(uint64_t), st));
-        RCK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemsetAsync(d_val_off, 0, sizeof(uint64_t), st));
+        CLY_CKG(hipStreamSynchronize(st));
         return CLY_OK;
     }
-    RCK(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));      // (timing only)
-    RCK(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
-    RCK(cly_rd_scratch_internal(ctx, RS_TAB, sizeof(uint32_t) * RT_WORDS, (void**)&d_tab));
-    RCK(cly_rd_scratch_internal(ctx, RS_FILES, sizeof(RdFile) * (size_t)nfiles, (void**)&d_files));
-    RCK(cly_rd_scratch_internal(ctx, RS_SPAN, sizeof(RdSpan) * n, (void**)&d_span));
-    RCK(cly_rd_scratch_internal(ctx, RS_CNT, sizeof(uint64_t) * (n + 1), (void**)&d_cnt));
-    RCK(cly_rd_scratch_internal(ctx, RS_POFS, sizeof(uint64_t) * (n + 1), (void**)&d_pofs));
-    RCK(cly_rd_scratch_internal(ctx, RS_MULTI, sizeof(uint64_t) * n, (void**)&d_multi));
-    RCK(cly_rd_scratch_internal(ctx, RS_TOT, sizeof(RdTot), (void**)&d_tot));
-    RCK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_pofs, (uint64_t)0, (size_t)(n + 1),
-                                rocprim::plus<uint64_t>(), st));
-    RCK(cly_rd_scratch_internal(ctx, RS_TMP, tmp_bytes, &d_tmp));
-    RCK(hipMemcpyAsync(d_tab, const_table(), sizeof(uint32_t) * RT_WORDS, hipMemcpyHostToDevice, st));
-    if (nfiles) RCK(hipMemcpyAsync(d_files, sorted.data(), sizeof(RdFile) * (size_t)nfiles, hipMemcpyHostToDevice, st));
-    RCK(hipEventRecord(e0, st));
-    RCK(hipMemsetAsync(d_tot, 0, sizeof(RdTot), st));
+    CLY_CKG(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));      // (timing only)
+    CLY_CKG(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
+    CLY_CKG(cly_scratch(ctx, RS_TAB, sizeof(uint32_t) * RT_WORDS, &d_tab));
+    CLY_CKG(cly_scratch(ctx, RS_FILES, sizeof(RdFile) * (size_t)nfiles, &d_files));
+    CLY_CKG(cly_scratch(ctx, RS_SPAN, sizeof(RdSpan) * n, &d_span));
+    CLY_CKG(cly_scratch(ctx, RS_CNT, sizeof(uint64_t) * (n + 1), &d_cnt));
+    CLY_CKG(cly_scratch(ctx, RS_POFS, sizeof(uint64_t) * (n + 1), &d_pofs));
+    CLY_CKG(cly_scratch(ctx, RS_MULTI, sizeof(uint64_t) * n, &d_multi));
+    CLY_CKG(cly_scratch(ctx, RS_TOT, sizeof(RdTot), &d_tot));
+    CLY_CKG(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_pofs, (uint64_t)0, (size_t)(n + 1),
+                                    rocprim::plus<uint64_t>(), st));
+    CLY_CKG(cly_scratch(ctx, RS_TMP, tmp_bytes, &d_tmp));
+    CLY_CKG(hipMemcpyAsync(d_tab, const_table(), sizeof(uint32_t) * RT_WORDS, hipMemcpyHostToDevice, st));
+    if (nfiles) CLY_CKG(hipMemcpyAsync(d_files, sorted.data(), sizeof(RdFile) * (size_t)nfiles, hipMemcpyHostToDevice, st));
+    CLY_CKG(hipEventRecord(e0, st));
+    CLY_CKG(hipMemsetAsync(d_tot, 0, sizeof(RdTot), st));
     {
         const unsigned grid = (unsigned)((n + 1 + RD_NT - 1) / RD_NT);
         k_rd_hdr<<<grid, RD_NT, 0, st>>>(n, d_pos, d_files, nfiles, d_tuples, d_status, d_span, d_cnt);
-        RCK(hipGetLastError());
+        CLY_CKG(hipGetLastError());
         size_t tb = tmp_bytes;
-        RCK(rocprim::exclusive_scan(d_tmp, tb, d_cnt, d_pofs, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
+        CLY_CKG(rocprim::exclusive_scan(d_tmp, tb, d_cnt, d_pofs, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
         k_rd_plan<<<grid, RD_NT, 0, st>>>(n, d_pofs, d_multi, d_tot);
-        RCK(hipGetLastError());
+        CLY_CKG(hipGetLastError());
         // the sizes of the hot pass: one small read-back
-        RCK(hipMemcpyAsync(&P, d_pofs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        RCK(hipMemcpyAsync(&tot, d_tot, sizeof(RdTot), hipMemcpyDeviceToHost, st));
-        RCK(hipStreamSynchronize(st));
+        CLY_CKG(hipMemcpyAsync(&P, d_pofs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipMemcpyAsync(&tot, d_tot, sizeof(RdTot), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         const uint64_t ngroups = (P + 63) >> 6;
         const unsigned pgrid = (unsigned)((ngroups + (RD_NT / 64) * RD_IT - 1) / ((RD_NT / 64) * RD_IT));
         if (P) {
-            RCK(cly_rd_scratch_internal(ctx, RS_SLOT, sizeof(uint32_t) * 2 * ngroups, (void**)&d_slot));
+            CLY_CKG(cly_scratch(ctx, RS_SLOT, sizeof(uint32_t) * 2 * ngroups, &d_slot));
             k_rd_crc<<<pgrid, RD_NT, 0, st>>>(n, P, d_pofs, d_span, d_tab, d_status, d_slot);
-            RCK(hipGetLastError());
+            CLY_CKG(hipGetLastError());
             if (tot.n_multi) {
                 k_rd_finish<<<(unsigned)tot.n_multi, 64, 0, st>>>(tot.n_multi, d_multi, d_pofs, d_span, d_slot, d_status);
-                RCK(hipGetLastError());
+                CLY_CKG(hipGetLastError());
             }
         }
         k_rd_vs<<<grid, RD_NT, 0, st>>>(n, d_pos, d_status, d_span, d_tuples, d_cnt, d_tot);
-        RCK(hipGetLastError());
+        CLY_CKG(hipGetLastError());
         tb = tmp_bytes;
-        RCK(rocprim::exclusive_scan(d_tmp, tb, d_cnt, d_val_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
-        RCK(hipMemcpyAsync(&tot, d_tot, sizeof(RdTot), hipMemcpyDeviceToHost, st));
-        RCK(hipStreamSynchronize(st));
+        CLY_CKG(rocprim::exclusive_scan(d_tmp, tb, d_cnt, d_val_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
+        CLY_CKG(hipMemcpyAsync(&tot, d_tot, sizeof(RdTot), hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
         rr->n_rec = tot.n_rec; rr->n_eof = tot.n_eof; rr->n_crc = tot.n_crc; rr->n_other = tot.n_other;
         rr->n_nofile = tot.n_nofile; rr->value_bytes = tot.value_bytes; rr->record_bytes = tot.record_bytes;
         if (want_values && tot.value_bytes > values_cap) rc = CLY_ERR_CAPACITY;
         else if (want_values && tot.value_bytes && P) {
             if (own_values) {
-                RCK(cly_rd_scratch_internal(ctx, RS_H_VAL, tot.value_bytes, (void**)&d_values));
+                CLY_CKG(cly_scratch(ctx, RS_H_VAL, tot.value_bytes, &d_values));
                 *own_values = d_values;
             }
             k_rd_gather<<<pgrid, RD_NT, 0, st>>>(n, P, d_pofs, d_span, d_status, d_val_off, d_values);
-            RCK(hipGetLastError());
+            CLY_CKG(hipGetLastError());
         }
     }
-    RCK(hipEventRecord(e1, st));
-    RCK(hipEventSynchronize(e1));
+    CLY_CKG(hipEventRecord(e1, st));
+    CLY_CKG(hipEventSynchronize(e1));
     {
         float ms = 0;
-        RCK(hipEventElapsedTime(&ms, e0, e1));
+        CLY_CKG(hipEventElapsedTime(&ms, e0, e1));
         rr->read_ms = ms;
     }
 done:
@@ -508,7 +500,7 @@ extern "C" int cly_read_device(cly_ctx* ctx, const cly_file* files, int nfiles, 
     std::vector<RdFile> sorted;
     const int rc = sort_files(files, nfiles, sorted);
     if (rc != CLY_OK) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : cly_ctx_stream_internal(ctx);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     return read_impl(ctx, sorted, d_pos, n, d_tuples, d_status, d_val_off, d_values, values_cap, nullptr, rr, st);
 }
 
@@ -519,8 +511,8 @@ extern "C" int cly_read(cly_ctx* ctx, const cly_file* files, int nfiles, const c
     std::vector<RdFile> sorted;
     int rc = sort_files(files, nfiles, sorted);
     if (rc != CLY_OK) return rc;
-    if (hipSetDevice(cly_ctx_device_internal(ctx)) != hipSuccess) return CLY_ERR_DEVICE;
-    hipStream_t st = cly_ctx_stream_internal(ctx);
+    if (hipSetDevice(ctx->device) != hipSuccess) return CLY_ERR_DEVICE;
+    hipStream_t st = ctx->stream;
     // stage only the files that a position names
     std::vector<uint8_t> named((size_t)nfiles, 0);
     for (uint64_t i = 0; i < n; i++) {
@@ -533,30 +525,30 @@ extern "C" int cly_read(cly_ctx* ctx, const cly_file* files, int nfiles, const c
     for (int i = 0; i < nfiles; i++) if (named[i]) { dev.push_back(sorted[i]); bytes += (sorted[i].len + 255) & ~255ull; }
     uint8_t* d_bytes = nullptr; cly_pos* d_pos = nullptr; cly_tuple* d_tup = nullptr; int32_t* d_status = nullptr;
     uint64_t* d_voff = nullptr; uint8_t* d_val = nullptr;
-    RCK(cly_rd_scratch_internal(ctx, RS_H_BYTES, bytes, (void**)&d_bytes));
-    RCK(cly_rd_scratch_internal(ctx, RS_H_POS, sizeof(cly_pos) * n, (void**)&d_pos));
-    if (tuples) RCK(cly_rd_scratch_internal(ctx, RS_H_TUP, sizeof(cly_tuple) * n, (void**)&d_tup));
-    RCK(cly_rd_scratch_internal(ctx, RS_H_STATUS, sizeof(int32_t) * n, (void**)&d_status));
-    RCK(cly_rd_scratch_internal(ctx, RS_H_VOFF, sizeof(uint64_t) * (n + 1), (void**)&d_voff));
+    CLY_CKG(cly_scratch(ctx, RS_H_BYTES, bytes, &d_bytes));
+    CLY_CKG(cly_scratch(ctx, RS_H_POS, sizeof(cly_pos) * n, &d_pos));
+    if (tuples) CLY_CKG(cly_scratch(ctx, RS_H_TUP, sizeof(cly_tuple) * n, &d_tup));
+    CLY_CKG(cly_scratch(ctx, RS_H_STATUS, sizeof(int32_t) * n, &d_status));
+    CLY_CKG(cly_scratch(ctx, RS_H_VOFF, sizeof(uint64_t) * (n + 1), &d_voff));
     {
         uint64_t at = 0;
         for (RdFile& f : dev) {
-            if (f.len) RCK(hipMemcpyAsync(d_bytes + at, (const void*)(uintptr_t)f.base, f.len, hipMemcpyHostToDevice, st));
+            if (f.len) CLY_CKG(hipMemcpyAsync(d_bytes + at, (const void*)(uintptr_t)f.base, f.len, hipMemcpyHostToDevice, st));
             f.base = (uint64_t)(uintptr_t)(d_bytes + at);
             at += (f.len + 255) & ~255ull;
         }
     }
-    if (n) RCK(hipMemcpyAsync(d_pos, pos, sizeof(cly_pos) * n, hipMemcpyHostToDevice, st));
+    if (n) CLY_CKG(hipMemcpyAsync(d_pos, pos, sizeof(cly_pos) * n, hipMemcpyHostToDevice, st));
     rc = read_impl(ctx, dev, d_pos, n, d_tup, d_status, d_voff, nullptr, values ? values_cap : 0,
                    values ? &d_val : nullptr, rr, st);
     if (rc == CLY_OK || rc == CLY_ERR_CAPACITY) {
         const int rc0 = rc;
-        if (n && tuples) RCK(hipMemcpyAsync(tuples, d_tup, sizeof(cly_tuple) * n, hipMemcpyDeviceToHost, st));
-        if (n) RCK(hipMemcpyAsync(status, d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        RCK(hipMemcpyAsync(val_off, d_voff, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, st));
+        if (n && tuples) CLY_CKG(hipMemcpyAsync(tuples, d_tup, sizeof(cly_tuple) * n, hipMemcpyDeviceToHost, st));
+        if (n) CLY_CKG(hipMemcpyAsync(status, d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipMemcpyAsync(val_off, d_voff, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, st));
         if (rc0 == CLY_OK && d_val && rr->value_bytes)
-            RCK(hipMemcpyAsync(values, d_val, rr->value_bytes, hipMemcpyDeviceToHost, st));
-        RCK(hipStreamSynchronize(st));
+            CLY_CKG(hipMemcpyAsync(values, d_val, rr->value_bytes, hipMemcpyDeviceToHost, st));
+        CLY_CKG(hipStreamSynchronize(st));
     }
 done:
     return rc;

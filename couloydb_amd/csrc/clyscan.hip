@@ -49,9 +49,13 @@
 
 #include <algorithm>
 #include <atomic>
+#include <new>
 #include <thread>
+#include <vector>
 
 #include "scan_core.h"
+#define CLY_TAG "clyscan"
+#include "cly_internal.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -2368,12 +2372,8 @@ k_fin(const DevFile* __restrict__ files, FileInfo* finfo, const uint32_t* __rest
 
 // ---------------------------------------------------------------------------
 // Host side
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    fprintf(stderr, "clyscan: %s failed: %s\n", #x, hipGetErrorString(e_)); return CLY_ERR_DEVICE; } } while (0)
-
-struct cly_ctx {
-    int device;
-    hipStream_t stream;
+// The scan's part of a context (cly_ctx::scan, cly_internal.h), private to this file.
+struct cly_scan_state {
     hipEvent_t ev[8];
     uint8_t* d_call; uint8_t* h_call; size_t call_bytes;     // the per-call block (ensure_files)
     DevFile* d_files; uint32_t* d_tprefix; FileInfo* d_finfo; uint64_t* d_ftotal; int cap_files;
@@ -2392,80 +2392,76 @@ struct cly_ctx {
     float kms[6];                // last call: k_scan, link rounds (k_link/k_refix), k_emit, k_fin, discarded attempts, all
     uint8_t* d_bytes; uint64_t cap_bytes;          // host-path staging
     cly_tuple* d_tuples; uint64_t cap_tuples;
-    void* merge_scratch;         // clymerge.hip's buffers (grow-only)
-    int64_t now_ns;              // loadIndex's time.Now() for the TTL sweep (0: the wall clock per call)
     int dbg;                     // cly_dbg_set: bit 0 = keep k_scan's LOCALs (before any repair) in d_dbg,
                                  // bit 1 = print the repair rounds, bit 2 = per-kernel timing markers
     TileLocal* d_dbg; int64_t cap_dbg;
 };
-extern "C" void cly_merge_scratch_free(void* p);
 
-extern "C" int cly_ctx_create(int device, cly_ctx** out) {
-    if (!out) return CLY_ERR_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return CLY_ERR_DEVICE;
-    HIPCK(hipSetDevice(device));
-    cly_ctx* c = (cly_ctx*)calloc(1, sizeof(cly_ctx));
-    if (!c) return CLY_ERR_DEVICE;
-    c->device = device;
-    HIPCK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+static void build_tables(uint32_t* hn) {
+    for (int k = 0; k < NTAB_ALL / 128; k++) {
+        uint64_t nbytes;
+        if (k < 64) nbytes = (uint64_t)(k & 15) << (4 * (k >> 4));               // A^(v 16^d)
+        else if (k == 64) nbytes = 65536;                                        // A^65536
+        else if (k == 65) nbytes = (uint64_t)CLY_TILE;                           // k_fin's tile step
+        else if (k >= TAB_PW / 128) nbytes = (uint64_t)CLY_TILE << (k - TAB_PW / 128);   // k_fin's levels
+        else {
+            const int e = k - 66;                                                // TAB_EM
+            if (e < EM_F1) nbytes = 4ull * (uint64_t)(e + 1);                    // A^(4k), k = 1..16
+            else if (e < EM_RUN) nbytes = (uint64_t)(e - EM_F1 + 1);             // A^1..A^3
+            else if (e < EM_SEGP) nbytes = (uint64_t)RUN_BYTES << (e - EM_RUN);  // A^(RUN_BYTES 2^l)
+            else nbytes = 64ull << (e - EM_SEGP + 1);                            // A^128, A^256, A^512
+        }
+        const uint32_t xm = cly_x8n(nbytes);
+        for (int nb = 0; nb < 8; nb++)
+            for (uint32_t v = 0; v < 16; v++) hn[k * 128 + nb * 16 + v] = cly_multmodp(xm, v << (4 * nb));
+    }
+}
+
+// Eager: the events, the tables on the device and the grids of k_scan / k_emit
+static int scan_state_init(cly_scan_state* s, int device) {
     // timing-only markers: no system-scope fence (its L2 writeback and
     // invalidate left a 6-us gap after every marked kernel); the results come
     // back by copies and stream waits
-    for (int i = 0; i < 8; i++) HIPCK(hipEventCreateWithFlags(&c->ev[i], hipEventDisableSystemFence));
-    {
-        static uint32_t hn[NTAB_ALL];
-        for (int k = 0; k < NTAB_ALL / 128; k++) {
-            uint64_t nbytes;
-            if (k < 64) nbytes = (uint64_t)(k & 15) << (4 * (k >> 4));               // A^(v 16^d)
-            else if (k == 64) nbytes = 65536;                                        // A^65536
-            else if (k == 65) nbytes = (uint64_t)CLY_TILE;                           // k_fin's tile step
-            else if (k >= TAB_PW / 128) nbytes = (uint64_t)CLY_TILE << (k - TAB_PW / 128);   // k_fin's levels
-            else {
-                const int e = k - 66;                                                // TAB_EM
-                if (e < EM_F1) nbytes = 4ull * (uint64_t)(e + 1);                    // A^(4k), k = 1..16
-                else if (e < EM_RUN) nbytes = (uint64_t)(e - EM_F1 + 1);             // A^1..A^3
-                else if (e < EM_SEGP) nbytes = (uint64_t)RUN_BYTES << (e - EM_RUN);  // A^(RUN_BYTES 2^l)
-                else nbytes = 64ull << (e - EM_SEGP + 1);                            // A^128, A^256, A^512
-            }
-            const uint32_t xm = cly_x8n(nbytes);
-            for (int nb = 0; nb < 8; nb++)
-                for (uint32_t v = 0; v < 16; v++) hn[k * 128 + nb * 16 + v] = cly_multmodp(xm, v << (4 * nb));
-        }
-        HIPCK(hipMalloc(&c->d_tabs, sizeof(hn)));
-        HIPCK(hipMemcpy(c->d_tabs, hn, sizeof(hn), hipMemcpyHostToDevice));
-    }
-    {
-        int ncu = 0;
-        HIPCK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        int per_cu = 0;
-        HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_scan, 64 * SCAN_WAVES, 0));
-        if (per_cu < 1) per_cu = 1;
-        c->scan_grid = per_cu * ncu;
-        per_cu = 0;
-        HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_emit, 64 * EMIT_WAVES, 0));
-        if (per_cu < 1) per_cu = 1;
-        c->emit_grid = per_cu * ncu;
-        c->loc_grid = ncu;
-    }
-    *out = c;
+    for (int i = 0; i < 8; i++) CLY_CK(hipEventCreateWithFlags(&s->ev[i], hipEventDisableSystemFence));
+    static uint32_t hn[NTAB_ALL];
+    build_tables(hn);
+    CLY_CK(hipMalloc(&s->d_tabs, sizeof(hn)));
+    CLY_CK(hipMemcpy(s->d_tabs, hn, sizeof(hn), hipMemcpyHostToDevice));
+    int ncu = 0;
+    CLY_CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    int per_cu = 0;
+    CLY_CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_scan, 64 * SCAN_WAVES, 0));
+    if (per_cu < 1) per_cu = 1;
+    s->scan_grid = per_cu * ncu;
+    per_cu = 0;
+    CLY_CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_emit, 64 * EMIT_WAVES, 0));
+    if (per_cu < 1) per_cu = 1;
+    s->emit_grid = per_cu * ncu;
+    s->loc_grid = ncu;
     return CLY_OK;
 }
 
-extern "C" void cly_ctx_destroy(cly_ctx* c) {
-    if (!c) return;
-    hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    hipFree(c->d_call); hipFree(c->d_ftotal);
-    hipFree(c->d_loc); hipFree(c->d_tin); hipFree(c->d_treg); hipFree(c->d_fix); hipFree(c->d_rec);
-    hipFree(c->d_seg); hipFree(c->d_chunks); hipFree(c->d_lmask); hipFree(c->d_sp_rec);
-    hipFree(c->d_tabs); hipFree(c->d_bytes); hipFree(c->d_tuples); hipFree(c->d_dbg);
-    hipHostFree(c->h_call);
-    cly_merge_scratch_free(c->merge_scratch);
-    for (int i = 0; i < 8; i++) hipEventDestroy(c->ev[i]);
-    hipStreamDestroy(c->stream);
-    free(c);
+// (also the tear-down of a half-built state: every member may still be null)
+extern "C" void cly_scan_state_destroy_internal(cly_scan_state* s) {
+    if (!s) return;
+    hipFree(s->d_call); hipFree(s->d_ftotal);
+    hipFree(s->d_loc); hipFree(s->d_tin); hipFree(s->d_treg); hipFree(s->d_fix); hipFree(s->d_rec);
+    hipFree(s->d_seg); hipFree(s->d_chunks); hipFree(s->d_lmask); hipFree(s->d_sp_rec);
+    hipFree(s->d_tabs); hipFree(s->d_bytes); hipFree(s->d_tuples); hipFree(s->d_dbg);
+    hipHostFree(s->h_call);
+    for (int i = 0; i < 8; i++) if (s->ev[i]) hipEventDestroy(s->ev[i]);
+    free(s);
+}
+
+// (the caller, cly_ctx_create, has made `device` current)
+extern "C" int cly_scan_state_create_internal(int device, cly_scan_state** out) {
+    *out = nullptr;
+    cly_scan_state* s = (cly_scan_state*)calloc(1, sizeof(cly_scan_state));
+    if (!s) return CLY_ERR_DEVICE;
+    const int rc = scan_state_init(s, device);
+    if (rc != CLY_OK) { cly_scan_state_destroy_internal(s); return rc; }
+    *out = s;
+    return CLY_OK;
 }
 
 extern "C" uint64_t cly_scan_capacity(const cly_file* files, int nfiles) {
@@ -2479,93 +2475,94 @@ extern "C" uint64_t cly_scan_capacity(const cly_file* files, int nfiles) {
 // call moves its inputs (and zeroes the outputs) with one copy in and reads
 // the results back with one copy out.
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-static int ensure_files(cly_ctx* c, int nfiles) {
-    if (nfiles <= c->cap_files) return CLY_OK;
-    hipFree(c->d_call); hipFree(c->d_ftotal); hipHostFree(c->h_call);
-    c->d_call = nullptr; c->h_call = nullptr; c->d_ftotal = nullptr;
-    c->cap_files = 0;
+static int ensure_files(cly_scan_state* s, int nfiles) {
+    if (nfiles <= s->cap_files) return CLY_OK;
+    hipFree(s->d_call); hipFree(s->d_ftotal); hipHostFree(s->h_call);
+    s->d_call = nullptr; s->h_call = nullptr; s->d_ftotal = nullptr;
+    s->cap_files = 0;
     const int cap = nfiles < 64 ? 64 : nfiles;
     const size_t o_fi = al16(sizeof(Globals)), o_f = o_fi + al16(sizeof(FileInfo) * cap);
     const size_t o_tp = o_f + al16(sizeof(DevFile) * cap), o_rp = o_tp + al16(sizeof(uint32_t) * (cap + 1));
     const size_t tot = o_rp + al16(sizeof(uint32_t) * (cap + 1));
-    HIPCK(hipMalloc(&c->d_call, tot));
-    HIPCK(hipMalloc(&c->d_ftotal, sizeof(uint64_t) * cap));
-    HIPCK(hipHostMalloc(&c->h_call, tot, hipHostMallocDefault));
-    c->d_g = (Globals*)c->d_call; c->h_g = (Globals*)c->h_call;
-    c->d_finfo = (FileInfo*)(c->d_call + o_fi); c->h_finfo = (FileInfo*)(c->h_call + o_fi);
-    c->d_files = (DevFile*)(c->d_call + o_f); c->h_files = (DevFile*)(c->h_call + o_f);
-    c->d_tprefix = (uint32_t*)(c->d_call + o_tp); c->h_tprefix = (uint32_t*)(c->h_call + o_tp);
-    c->d_rprefix = (uint32_t*)(c->d_call + o_rp); c->h_rprefix = (uint32_t*)(c->h_call + o_rp);
-    c->call_bytes = tot;
-    c->cap_files = cap;
+    CLY_CK(hipMalloc(&s->d_call, tot));
+    CLY_CK(hipMalloc(&s->d_ftotal, sizeof(uint64_t) * cap));
+    CLY_CK(hipHostMalloc(&s->h_call, tot, hipHostMallocDefault));
+    s->d_g = (Globals*)s->d_call; s->h_g = (Globals*)s->h_call;
+    s->d_finfo = (FileInfo*)(s->d_call + o_fi); s->h_finfo = (FileInfo*)(s->h_call + o_fi);
+    s->d_files = (DevFile*)(s->d_call + o_f); s->h_files = (DevFile*)(s->h_call + o_f);
+    s->d_tprefix = (uint32_t*)(s->d_call + o_tp); s->h_tprefix = (uint32_t*)(s->h_call + o_tp);
+    s->d_rprefix = (uint32_t*)(s->d_call + o_rp); s->h_rprefix = (uint32_t*)(s->h_call + o_rp);
+    s->call_bytes = tot;
+    s->cap_files = cap;
     return CLY_OK;
 }
 
-static int ensure_tiles(cly_ctx* c, int64_t ntiles) {
-    if (ntiles <= c->cap_tiles) return CLY_OK;
-    hipFree(c->d_loc); hipFree(c->d_tin); hipFree(c->d_treg); hipFree(c->d_fix); hipFree(c->d_rec);
-    hipFree(c->d_seg); hipFree(c->d_chunks); hipFree(c->d_lmask);
-    c->d_lmask = nullptr; c->lmask_words = 0;
-    c->d_loc = nullptr; c->d_tin = nullptr; c->d_treg = nullptr; c->d_fix = nullptr; c->d_rec = nullptr;
-    c->d_seg = nullptr; c->d_chunks = nullptr;
-    c->cap_tiles = 0;
+static int ensure_tiles(cly_scan_state* s, int64_t ntiles) {
+    if (ntiles <= s->cap_tiles) return CLY_OK;
+    hipFree(s->d_loc); hipFree(s->d_tin); hipFree(s->d_treg); hipFree(s->d_fix); hipFree(s->d_rec);
+    hipFree(s->d_seg); hipFree(s->d_chunks); hipFree(s->d_lmask);
+    s->d_lmask = nullptr; s->lmask_words = 0;
+    s->d_loc = nullptr; s->d_tin = nullptr; s->d_treg = nullptr; s->d_fix = nullptr; s->d_rec = nullptr;
+    s->d_seg = nullptr; s->d_chunks = nullptr;
+    s->cap_tiles = 0;
     const int64_t cap = ntiles < 1024 ? 1024 : ntiles;
-    HIPCK(hipMalloc(&c->d_loc, sizeof(TileLocal) * cap));
-    HIPCK(hipMalloc(&c->d_tin, sizeof(TileIn) * cap));
-    HIPCK(hipMalloc(&c->d_treg, sizeof(uint32_t) * 2 * cap));
-    HIPCK(hipMalloc(&c->d_seg, sizeof(uint32_t) * NSEG * (uint64_t)cap));
-    HIPCK(hipMalloc(&c->d_chunks, sizeof(uint32_t) * CH_WORDS * (uint64_t)cap));
-    HIPCK(hipMalloc(&c->d_fix, sizeof(uint32_t) * cap));
-    HIPCK(hipMalloc(&c->d_rec, sizeof(uint32_t) * 4 * (uint64_t)CAP_T * cap));
-    c->cap_tiles = cap;
+    CLY_CK(hipMalloc(&s->d_loc, sizeof(TileLocal) * cap));
+    CLY_CK(hipMalloc(&s->d_tin, sizeof(TileIn) * cap));
+    CLY_CK(hipMalloc(&s->d_treg, sizeof(uint32_t) * 2 * cap));
+    CLY_CK(hipMalloc(&s->d_seg, sizeof(uint32_t) * NSEG * (uint64_t)cap));
+    CLY_CK(hipMalloc(&s->d_chunks, sizeof(uint32_t) * CH_WORDS * (uint64_t)cap));
+    CLY_CK(hipMalloc(&s->d_fix, sizeof(uint32_t) * cap));
+    CLY_CK(hipMalloc(&s->d_rec, sizeof(uint32_t) * 4 * (uint64_t)CAP_T * cap));
+    s->cap_tiles = cap;
     return CLY_OK;
 }
 // k_link's global bitmasks (files of more than LINK_MAXT tiles): file f's words
 // start at first_tile / 32 + f, so no two files share one
-static int ensure_lmask(cly_ctx* c, int64_t ntiles, int nfiles) {
+static int ensure_lmask(cly_scan_state* s, int64_t ntiles, int nfiles) {
     const uint64_t words = (uint64_t)ntiles / 32 + (uint64_t)nfiles + 2;
-    if (words <= c->lmask_words) return CLY_OK;
-    hipFree(c->d_lmask);
-    c->d_lmask = nullptr; c->lmask_words = 0;
-    HIPCK(hipMalloc(&c->d_lmask, sizeof(uint32_t) * 2 * words));
-    c->lmask_words = words;
+    if (words <= s->lmask_words) return CLY_OK;
+    hipFree(s->d_lmask);
+    s->d_lmask = nullptr; s->lmask_words = 0;
+    CLY_CK(hipMalloc(&s->d_lmask, sizeof(uint32_t) * 2 * words));
+    s->lmask_words = words;
     return CLY_OK;
 }
 
 // The spill pool: at least `chunks` chunks (grow-only; the first call of a
 // context sizes it for one chunk per 8 tiles)
-static int ensure_spill(cly_ctx* c, uint64_t chunks) {
-    if (chunks <= c->cap_spill) return CLY_OK;
+static int ensure_spill(cly_scan_state* s, uint64_t chunks) {
+    if (chunks <= s->cap_spill) return CLY_OK;
     if (chunks > 0xFFFFFFF0ull) return CLY_ERR_ARG;
-    hipFree(c->d_sp_rec);
-    c->d_sp_rec = nullptr; c->cap_spill = 0;
-    HIPCK(hipMalloc(&c->d_sp_rec, sizeof(u32x4) * CAP_T * chunks));
-    c->cap_spill = (uint32_t)chunks;
+    hipFree(s->d_sp_rec);
+    s->d_sp_rec = nullptr; s->cap_spill = 0;
+    CLY_CK(hipMalloc(&s->d_sp_rec, sizeof(u32x4) * CAP_T * chunks));
+    s->cap_spill = (uint32_t)chunks;
     return CLY_OK;
 }
 
 // the largest file length: u64 chain positions in TileIn keep 48 bits (P_NONE above them)
 #define MAX_FILE_LEN ((1ull << 47) - 1)
 
-// alloc != nullptr: the output is allocated here (hipMalloc, the caller frees
-// it) once the link knows the exact record count, so that it holds exactly
-// needed + 16 tuples (d_out and out_cap are ignored).
-static int scan_attempt(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple* d_out, uint64_t out_cap,
-                        uint64_t* file_first, cly_file_result* res, uint64_t* needed, cly_stats* stats, void* stream_v,
-                        cly_tuple** alloc, uint64_t* alloc_cap) {
-    if (!c || (!files && nfiles) || nfiles < 0 || !res || !file_first) return CLY_ERR_ARG;
-    if (alloc) { *alloc = nullptr; d_out = nullptr; out_cap = 0; }
-    if (nfiles == 0) { if (needed) *needed = 0; return CLY_OK; }
-    HIPCK(hipSetDevice(c->device));
-    hipStream_t st = stream_v ? (hipStream_t)stream_v : c->stream;
-    int rc = ensure_files(c, nfiles);
-    if (rc) return rc;
-    int64_t ntiles = 0, nruns = 0;
-    uint64_t bytes = 0;
-    // the run length: the longest (up to RUN_TILES) whose runs fill the wave slots
+// One attempt of a scan call (scan_once) is the steps below, in this order:
+//   scan_plan, scan_reserve     geometry, the per-call block's host mirror, the tile buffers
+//   scan_launch                 upload, k_scan, k_link, k_refix, k_link (no host wait)
+//   scan_emit                   k_emit, k_fin, the read-back and the call's one wait
+//   scan_repair                 only if the device's repair round left tiles listed
+//   scan_times, scan_decode     the timers and the per-file results
+struct ScanGeom {
+    int64_t ntiles, nruns;       // over all files
+    uint32_t run_tiles;          // k_scan's run length
+    uint64_t bytes;
+};
+struct ScanOut { cly_tuple* d_out; uint64_t cap; };         // k_emit's output buffer
+struct ScanTimes { float scan, link, emit, fin, fix; };     // ms; fix: the host repair loop
+
+// The run length (the longest, up to RUN_TILES, whose runs fill the wave
+// slots) and the files' tiles and runs: h_files, h_tprefix, h_rprefix
+static int scan_plan(cly_scan_state* s, const cly_file* files, int nfiles, ScanGeom* g) {
     uint32_t rt = RUN_TILES;
     if (CLY_RUN_ADAPT) {
-        const int64_t slots = (int64_t)c->scan_grid * SCAN_WAVES;
+        const int64_t slots = (int64_t)s->scan_grid * SCAN_WAVES;
         for (; rt > 1; rt >>= 1) {
             int64_t nr = 0;
             for (int i = 0; i < nfiles; i++) {
@@ -2575,173 +2572,192 @@ static int scan_attempt(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple
             if (nr >= slots) break;
         }
     }
+    int64_t ntiles = 0, nruns = 0;
+    uint64_t bytes = 0;
     for (int i = 0; i < nfiles; i++) {
         if (files[i].len > MAX_FILE_LEN) return CLY_ERR_ARG;
         if (files[i].len && (((uintptr_t)files[i].base) & 15)) return CLY_ERR_ARG;
         const uint64_t nt = files[i].len ? (files[i].len + CLY_TILE - 1) / CLY_TILE : 1;
-        c->h_files[i].base = files[i].base;
-        c->h_files[i].len = files[i].len;
-        c->h_files[i].fid = files[i].fid;
-        c->h_files[i].first_tile = (uint32_t)ntiles;
-        c->h_files[i].ntile = (uint32_t)nt;
-        c->h_files[i]._pad = 0;
-        c->h_tprefix[i] = (uint32_t)ntiles;
-        c->h_rprefix[i] = (uint32_t)nruns;
+        s->h_files[i].base = files[i].base;
+        s->h_files[i].len = files[i].len;
+        s->h_files[i].fid = files[i].fid;
+        s->h_files[i].first_tile = (uint32_t)ntiles;
+        s->h_files[i].ntile = (uint32_t)nt;
+        s->h_files[i]._pad = 0;
+        s->h_tprefix[i] = (uint32_t)ntiles;
+        s->h_rprefix[i] = (uint32_t)nruns;
         ntiles += (int64_t)nt;
         nruns += (int64_t)((nt + rt - 1) / rt);
         bytes += files[i].len;
     }
     if (ntiles >= (1LL << 31)) return CLY_ERR_ARG;
-    c->h_tprefix[nfiles] = (uint32_t)ntiles;
-    c->h_rprefix[nfiles] = (uint32_t)nruns;
-    rc = ensure_tiles(c, ntiles);
+    s->h_tprefix[nfiles] = (uint32_t)ntiles;
+    s->h_rprefix[nfiles] = (uint32_t)nruns;
+    g->ntiles = ntiles; g->nruns = nruns; g->run_tiles = rt; g->bytes = bytes;
+    return CLY_OK;
+}
+
+// The tile buffers, k_link's bitmasks (only with a file past LINK_MAXT tiles) and the spill pool
+static int scan_reserve(cly_scan_state* s, int nfiles, const ScanGeom& g) {
+    int rc = ensure_tiles(s, g.ntiles);
     if (rc) return rc;
-    {
-        bool far = false;
-        for (int i = 0; i < nfiles; i++) far |= c->h_files[i].ntile > LINK_MAXT;
-        if (far && (rc = ensure_lmask(c, ntiles, nfiles))) return rc;
-    }
-    rc = ensure_spill(c, (uint64_t)ntiles / 8 + 64);
-    if (rc) return rc;
-    memset(c->h_g, 0, sizeof(Globals));
-    c->h_g->spill_cap = c->cap_spill;
-    c->h_g->run_tiles = rt;
-    memset(c->h_finfo, 0, sizeof(FileInfo) * nfiles);
-    for (int i = 0; i < nfiles; i++) c->h_finfo[i].fail_off = c->h_finfo[i].fail_idx = ~0ull;
-    HIPCK(hipMemcpyAsync(c->d_call, c->h_call, c->call_bytes, hipMemcpyHostToDevice, st));
-    const uint32_t nt32 = (uint32_t)ntiles;
-    int grid = c->scan_grid;
-    if ((int64_t)grid * SCAN_WAVES > nruns) grid = (int)((nruns + SCAN_WAVES - 1) / SCAN_WAVES);
-    HIPCK(hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_scan, dim3(grid), dim3(64 * SCAN_WAVES), 0, st, c->d_files, nfiles, c->d_rprefix, (uint32_t)nruns,
-                       c->d_loc, c->d_rec, c->d_seg, c->d_treg, c->d_chunks, c->d_sp_rec, c->d_g);
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(c->ev[1], st));
-    if (c->dbg & 1) {
-        if (c->cap_dbg < ntiles) {
-            hipFree(c->d_dbg); c->d_dbg = nullptr; c->cap_dbg = 0;
-            HIPCK(hipMalloc(&c->d_dbg, sizeof(TileLocal) * ntiles));
-            c->cap_dbg = ntiles;
+    bool far = false;
+    for (int i = 0; i < nfiles; i++) far |= s->h_files[i].ntile > LINK_MAXT;
+    if (far && (rc = ensure_lmask(s, g.ntiles, nfiles))) return rc;
+    return ensure_spill(s, (uint64_t)g.ntiles / 8 + 64);
+}
+
+static void launch_link(cly_scan_state* s, hipStream_t st, int nfiles, int slot, int guard) {
+    hipLaunchKernelGGL(k_link, dim3(nfiles), dim3(LINK_NT), 0, st, s->d_files, nfiles, s->d_loc, s->d_tin, s->d_ftotal,
+                       s->d_finfo, s->d_fix, s->d_lmask, s->lmask_words, s->d_g, slot, guard);
+}
+static void launch_refix(cly_scan_state* s, hipStream_t st, int nfiles, unsigned grid, int slot) {
+    hipLaunchKernelGGL(k_refix, dim3(grid), dim3(64 * SCAN_WAVES), 0, st, s->d_files, nfiles, s->d_tprefix,
+                       s->d_loc, s->d_tin, s->d_rec, s->d_seg, s->d_treg, s->d_chunks, s->d_sp_rec,
+                       s->d_fix, s->d_g, slot);
+}
+
+// The per-call block goes up, then k_scan and the link without a host wait:
+// k_link (chain states, contradicted tiles, file bases; lists into nfix[0]),
+// one repair round on the device (k_refix of nfix[0], k_link into nfix[1];
+// both return at once when the first link listed no tile).
+static int scan_launch(cly_scan_state* s, hipStream_t st, int nfiles, const ScanGeom& g, bool detail) {
+    memset(s->h_g, 0, sizeof(Globals));
+    s->h_g->spill_cap = s->cap_spill;
+    s->h_g->run_tiles = g.run_tiles;
+    memset(s->h_finfo, 0, sizeof(FileInfo) * nfiles);
+    for (int i = 0; i < nfiles; i++) s->h_finfo[i].fail_off = s->h_finfo[i].fail_idx = ~0ull;
+    CLY_CK(hipMemcpyAsync(s->d_call, s->h_call, s->call_bytes, hipMemcpyHostToDevice, st));
+    int grid = s->scan_grid;
+    if ((int64_t)grid * SCAN_WAVES > g.nruns) grid = (int)((g.nruns + SCAN_WAVES - 1) / SCAN_WAVES);
+    CLY_CK(hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(k_scan, dim3(grid), dim3(64 * SCAN_WAVES), 0, st, s->d_files, nfiles, s->d_rprefix,
+                       (uint32_t)g.nruns, s->d_loc, s->d_rec, s->d_seg, s->d_treg, s->d_chunks, s->d_sp_rec, s->d_g);
+    CLY_CK(hipGetLastError());
+    CLY_CK(hipEventRecord(s->ev[1], st));
+    if (s->dbg & 1) {
+        if (s->cap_dbg < g.ntiles) {
+            hipFree(s->d_dbg); s->d_dbg = nullptr; s->cap_dbg = 0;
+            CLY_CK(hipMalloc(&s->d_dbg, sizeof(TileLocal) * g.ntiles));
+            s->cap_dbg = g.ntiles;
         }
-        HIPCK(hipMemcpyAsync(c->d_dbg, c->d_loc, sizeof(TileLocal) * ntiles, hipMemcpyDeviceToDevice, st));
+        CLY_CK(hipMemcpyAsync(s->d_dbg, s->d_loc, sizeof(TileLocal) * g.ntiles, hipMemcpyDeviceToDevice, st));
     }
-    // the link (k_link: chain states, contradicted tiles, file bases), then
-    // k_emit/k_fin, which return at once if the link listed tiles; only then
-    // the host waits.  Repair rounds (k_refix + k_link) follow on the host loop.
-    hipLaunchKernelGGL(k_link, dim3(nfiles), dim3(LINK_NT), 0, st, c->d_files, nfiles, c->d_loc, c->d_tin, c->d_ftotal,
-                       c->d_finfo, c->d_fix, c->d_lmask, c->lmask_words, c->d_g, 0, -1);
-    // one repair round on the device, without a host wait: k_refix and
-    // k_link return at once when the first link listed no tile
-    hipLaunchKernelGGL(k_refix, dim3(REFIX_GRID), dim3(64 * SCAN_WAVES), 0, st, c->d_files, nfiles, c->d_tprefix,
-                       c->d_loc, c->d_tin, c->d_rec, c->d_seg, c->d_treg, c->d_chunks, c->d_sp_rec,
-                       c->d_fix, c->d_g, 0);
-    hipLaunchKernelGGL(k_link, dim3(nfiles), dim3(LINK_NT), 0, st, c->d_files, nfiles, c->d_loc, c->d_tin, c->d_ftotal,
-                       c->d_finfo, c->d_fix, c->d_lmask, c->lmask_words, c->d_g, 1, 0);
-    HIPCK(hipGetLastError());
+    launch_link(s, st, nfiles, 0, -1);
+    launch_refix(s, st, nfiles, REFIX_GRID, 0);
+    launch_link(s, st, nfiles, 1, 0);
+    CLY_CK(hipGetLastError());
     // per-kernel markers between the link and k_emit and between k_emit and
     // k_fin only on request (cly_dbg_set bit 2: each marker costs a gap of
     // ~5 us); otherwise link + k_emit + k_fin are timed as one span
-    const bool detail = (c->dbg & 4) != 0;
-    if (detail) HIPCK(hipEventRecord(c->ev[2], st));
-    int slot = 1;
-    auto launch_emit = [&]() -> int {
-        int eg = c->emit_grid;
-        if ((int64_t)eg * EMIT_WAVES > ntiles) eg = (int)((ntiles + EMIT_WAVES - 1) / EMIT_WAVES);
-        hipLaunchKernelGGL(k_emit, dim3(eg), dim3(64 * EMIT_WAVES), 0, st, c->d_files, nfiles, c->d_tprefix, nt32,
-                           c->d_tin, c->d_loc, c->d_rec, c->d_seg, c->d_treg, c->d_finfo, c->d_tabs, d_out,
-                           out_cap, c->d_chunks, c->d_sp_rec, c->d_g, slot);
-        HIPCK(hipGetLastError());
-        if (detail) HIPCK(hipEventRecord(c->ev[3], st));
-        hipLaunchKernelGGL(k_fin, dim3(nfiles), dim3(FIN_NT), 0, st, c->d_files, c->d_finfo, c->d_treg, c->d_loc,
-                           c->d_tin, c->d_tabs, c->d_g, slot);
-        HIPCK(hipGetLastError());
-        HIPCK(hipEventRecord(c->ev[4], st));
-        // one read-back and one wait for the whole call when no repair round is needed
-        HIPCK(hipMemcpyAsync(c->h_call, c->d_call, (uint8_t*)(c->h_finfo + nfiles) - c->h_call, hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        return CLY_OK;
-    };
-    // (alloc: the output once the count is final, after any repair rounds)
-    auto emit_alloc = [&]() -> int {
-        out_cap = c->h_g->total + 16;
-        HIPCK(hipMalloc((void**)alloc, sizeof(cly_tuple) * out_cap));
-        d_out = *alloc;
-        if (alloc_cap) *alloc_cap = out_cap;
-        return launch_emit();
-    };
-    int rc2 = CLY_OK;
-    if (!alloc) rc2 = launch_emit();
-    else {
-        HIPCK(hipMemcpyAsync(c->h_g, c->d_g, sizeof(Globals), hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        if (!c->h_g->nfix[slot] && !c->h_g->fail && !c->h_g->spill_over) rc2 = emit_alloc();
+    if (detail) CLY_CK(hipEventRecord(s->ev[2], st));
+    return CLY_OK;
+}
+
+// k_emit and k_fin for the nfix list `slot` (both return at once if it lists
+// tiles), then one read-back and one wait for the whole call
+static int scan_emit(cly_scan_state* s, hipStream_t st, int nfiles, const ScanGeom& g, const ScanOut& o, int slot,
+                     bool detail) {
+    int eg = s->emit_grid;
+    if ((int64_t)eg * EMIT_WAVES > g.ntiles) eg = (int)((g.ntiles + EMIT_WAVES - 1) / EMIT_WAVES);
+    hipLaunchKernelGGL(k_emit, dim3(eg), dim3(64 * EMIT_WAVES), 0, st, s->d_files, nfiles, s->d_tprefix,
+                       (uint32_t)g.ntiles, s->d_tin, s->d_loc, s->d_rec, s->d_seg, s->d_treg, s->d_finfo, s->d_tabs,
+                       o.d_out, o.cap, s->d_chunks, s->d_sp_rec, s->d_g, slot);
+    CLY_CK(hipGetLastError());
+    if (detail) CLY_CK(hipEventRecord(s->ev[3], st));
+    hipLaunchKernelGGL(k_fin, dim3(nfiles), dim3(FIN_NT), 0, st, s->d_files, s->d_finfo, s->d_treg, s->d_loc,
+                       s->d_tin, s->d_tabs, s->d_g, slot);
+    CLY_CK(hipGetLastError());
+    CLY_CK(hipEventRecord(s->ev[4], st));
+    CLY_CK(hipMemcpyAsync(s->h_call, s->d_call, (uint8_t*)(s->h_finfo + nfiles) - s->h_call, hipMemcpyDeviceToHost, st));
+    CLY_CK(hipStreamSynchronize(st));
+    return CLY_OK;
+}
+// The allocating form (cly_scan_device_alloc_internal): the host already
+// holds the final record count, so the output is allocated here with exactly
+// total + 16 slots (*alloc; the caller frees it) and then emitted into.
+static int scan_emit_alloc(cly_scan_state* s, hipStream_t st, int nfiles, const ScanGeom& g, ScanOut* o, int slot,
+                           bool detail, cly_tuple** alloc, uint64_t* alloc_cap) {
+    o->cap = s->h_g->total + 16;
+    CLY_CK(hipMalloc((void**)alloc, sizeof(cly_tuple) * o->cap));
+    o->d_out = *alloc;
+    if (alloc_cap) *alloc_cap = o->cap;
+    return scan_emit(s, st, nfiles, g, *o, slot, detail);
+}
+
+// Host repair rounds while the last link still lists tiles: k_refix of the
+// list in nfix[*slot], k_link into the other list, a read-back of the
+// Globals and a wait; then *slot flips to the list just written.
+static int scan_repair(cly_scan_state* s, hipStream_t st, int nfiles, int* slot, uint32_t* rounds, uint32_t* refixed,
+                       float* ms_fix) {
+    CLY_CK(hipEventRecord(s->ev[5], st));
+    while (s->h_g->nfix[*slot]) {
+        if (s->h_g->fail) break;
+        if (*rounds > 4096) { fprintf(stderr, "clyscan: chain repair did not converge\n"); return CLY_ERR_NOREPAIR; }
+        const uint32_t nfix = s->h_g->nfix[*slot];
+        *refixed += nfix;
+        if (s->dbg & 2) fprintf(stderr, "clyscan: repair round %u: %u tiles listed, longest walk so far %u from tile %u\n",
+                                *rounds, nfix, s->h_g->walk_max, (uint32_t)s->h_g->walk_dbg);
+        const int ns = *slot ^ 1;
+        CLY_CK(hipMemsetAsync(&s->d_g->nfix[ns], 0, sizeof(uint32_t), st));
+        launch_refix(s, st, nfiles, (nfix + SCAN_WAVES - 1) / SCAN_WAVES, *slot);
+        launch_link(s, st, nfiles, ns, -1);
+        CLY_CK(hipGetLastError());
+        CLY_CK(hipMemcpyAsync(s->h_g, s->d_g, sizeof(Globals), hipMemcpyDeviceToHost, st));
+        CLY_CK(hipStreamSynchronize(st));
+        *slot = ns;
+        (*rounds)++;
     }
-    if (rc2) return rc2;
-    float ms_fix = 0;
-    uint32_t rounds = 1, refixed = 0;
-    if (c->h_g->nfix[0]) { rounds++; refixed += c->h_g->nfix[0]; }          // the device round
-    if ((c->dbg & 2) && c->h_g->nfix[0])
-        fprintf(stderr, "clyscan: device repair round: %u tiles listed, longest walk %u from tile %u\n", c->h_g->nfix[0],
-                c->h_g->walk_max, (uint32_t)c->h_g->walk_dbg);
-    if (c->h_g->nfix[slot]) {
-        HIPCK(hipEventRecord(c->ev[5], st));
-        while (c->h_g->nfix[slot]) {
-            if (c->h_g->fail) break;
-            if (rounds > 4096) { fprintf(stderr, "clyscan: chain repair did not converge\n"); return CLY_ERR_NOREPAIR; }
-            const uint32_t nfix = c->h_g->nfix[slot];
-            refixed += nfix;
-            if (c->dbg & 2) fprintf(stderr, "clyscan: repair round %u: %u tiles listed, longest walk so far %u from tile %u\n",
-                                    rounds, nfix, c->h_g->walk_max, (uint32_t)c->h_g->walk_dbg);
-            const int ns = slot ^ 1;
-            HIPCK(hipMemsetAsync(&c->d_g->nfix[ns], 0, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(k_refix, dim3((nfix + SCAN_WAVES - 1) / SCAN_WAVES), dim3(64 * SCAN_WAVES), 0, st,
-                               c->d_files, nfiles, c->d_tprefix, c->d_loc, c->d_tin, c->d_rec, c->d_seg,
-                               c->d_treg, c->d_chunks, c->d_sp_rec, c->d_fix, c->d_g, slot);
-            hipLaunchKernelGGL(k_link, dim3(nfiles), dim3(LINK_NT), 0, st, c->d_files, nfiles, c->d_loc, c->d_tin,
-                               c->d_ftotal, c->d_finfo, c->d_fix, c->d_lmask, c->lmask_words, c->d_g, ns, -1);
-            HIPCK(hipGetLastError());
-            HIPCK(hipMemcpyAsync(c->h_g, c->d_g, sizeof(Globals), hipMemcpyDeviceToHost, st));
-            HIPCK(hipStreamSynchronize(st));
-            slot = ns;
-            rounds++;
-        }
-        HIPCK(hipEventRecord(c->ev[6], st));
-        HIPCK(hipEventSynchronize(c->ev[6]));
-        HIPCK(hipEventElapsedTime(&ms_fix, c->ev[5], c->ev[6]));
-        if (!c->h_g->fail && !c->h_g->spill_over) {
-            HIPCK(hipEventRecord(c->ev[2], st));
-            rc2 = alloc ? emit_alloc() : launch_emit();
-            if (rc2) return rc2;
-        }
-    }
-    float ms_scan = 0, ms_link = 0, ms_emit = 0, ms_fin = 0;
-    if (c->h_g->spill_over) {                    // (k_emit / k_fin did not run: the caller runs the call again)
-        HIPCK(hipStreamSynchronize(st));
-        HIPCK(hipEventElapsedTime(&ms_scan, c->ev[0], c->ev[1]));
-        c->kms[5] = ms_scan + ms_fix;
-        return CLY_OK;
-    }
-    HIPCK(hipEventElapsedTime(&ms_scan, c->ev[0], c->ev[1]));
+    CLY_CK(hipEventRecord(s->ev[6], st));
+    CLY_CK(hipEventSynchronize(s->ev[6]));
+    CLY_CK(hipEventElapsedTime(ms_fix, s->ev[5], s->ev[6]));
+    return CLY_OK;
+}
+
+// The spans between the markers (t->fix is set by the caller).  Without
+// `detail`, link + k_emit + k_fin are one span from ev[1] to ev[4].  After a
+// host repair loop (t->fix > 0) ev[2] was re-recorded in front of the
+// relaunched k_emit, so the span before it is the repair's, not the link's.
+static int scan_times(cly_scan_state* s, bool detail, ScanTimes* t) {
+    const bool repaired = t->fix > 0;
+    CLY_CK(hipEventElapsedTime(&t->scan, s->ev[0], s->ev[1]));
     if (detail) {
-        HIPCK(hipEventElapsedTime(&ms_link, c->ev[1], c->ev[2]));
-        HIPCK(hipEventElapsedTime(&ms_emit, c->ev[2], c->ev[3]));
-        HIPCK(hipEventElapsedTime(&ms_fin, c->ev[3], c->ev[4]));
-        if (ms_fix > 0) ms_link = 0;   // ev[2] was re-recorded after the host repair loop
+        CLY_CK(hipEventElapsedTime(&t->link, s->ev[1], s->ev[2]));
+        CLY_CK(hipEventElapsedTime(&t->emit, s->ev[2], s->ev[3]));
+        CLY_CK(hipEventElapsedTime(&t->fin, s->ev[3], s->ev[4]));
+        if (repaired) t->link = 0;
     } else {
-        // one span: the link and k_emit + k_fin (after a host repair loop, ev[2]
-        // marks the relaunched k_emit)
-        HIPCK(hipEventElapsedTime(&ms_emit, ms_fix > 0 ? c->ev[2] : c->ev[1], c->ev[4]));
+        CLY_CK(hipEventElapsedTime(&t->emit, repaired ? s->ev[2] : s->ev[1], s->ev[4]));
     }
-    c->h_g->refix = refixed;
-    c->kms[0] = ms_scan; c->kms[1] = ms_link + ms_fix; c->kms[2] = ms_emit; c->kms[3] = ms_fin; c->kms[4] = 0;
-    c->kms[5] = ms_scan + ms_link + ms_fix + ms_emit + ms_fin;
-    if (c->h_g->fail) {
-        fprintf(stderr, "clyscan: internal error (code %#x)\n", c->h_g->fail);
-        return CLY_ERR_DEVICE;
-    }
-    uint64_t total = 0;
+    s->kms[0] = t->scan; s->kms[1] = t->link + t->fix; s->kms[2] = t->emit; s->kms[3] = t->fin; s->kms[4] = 0;
+    s->kms[5] = t->scan + t->link + t->fix + t->emit + t->fin;
+    return CLY_OK;
+}
+
+// A part's view ends VIEW_MAX past its first byte: a record of 2+ GiB that
+// starts there and passes the view's end reads as torn although the file
+// holds it whole.  Such a terminal (at offset T) is decoded again against the
+// whole file: a record there is beyond this library's limit (CLY_ERR_ARG), not
+// the io.EOF ReadLogRecord would not return.
+static int redecode_torn(const cly_file& f, int i, uint64_t T) {
+    const uint64_t x0 = (T / PART_BYTES) * PART_BYTES;
+    if (f.len - x0 <= VIEW_MAX) return CLY_OK;
+    uint8_t hb[26] = {0};
+    const uint64_t nh = f.len - T < 26 ? f.len - T : 26;
+    CLY_CK(hipMemcpy(hb, f.base + T, nh, hipMemcpyDeviceToHost));
+    const Hdr h = step_hdr((const uint8_t*)hb, 0, (int64_t)(f.len - T), (int64_t)T);
+    if (h.status != REC_OK) return CLY_OK;
+    fprintf(stderr, "clyscan: file %d: a record of %lld B at %llu crosses a part's 4-GiB view\n", i, (long long)h.size,
+            (unsigned long long)T);
+    return CLY_ERR_ARG;
+}
+
+// The per-file results from the FileInfos read back; *total: records over all files
+static int scan_decode(cly_scan_state* s, const cly_file* files, int nfiles, uint64_t* file_first, cly_file_result* res,
+                       uint64_t* total) {
+    *total = 0;
     for (int i = 0; i < nfiles; i++) {
-        const FileInfo& fi = c->h_finfo[i];
+        const FileInfo& fi = s->h_finfo[i];
         file_first[i] = fi.first_index;
         if (fi.fail_idx == ~0ull) {              // every record matches its CRC
             res[i].n_records = fi.end_index - fi.first_index;
@@ -2753,35 +2769,80 @@ static int scan_attempt(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple
             res[i].status = CLY_ERR_CRC;
         }
         res[i]._pad = 0;
-        total += res[i].n_records;
-        // A part's view ends VIEW_MAX past its first byte: a record of 2+ GiB that
-        // starts there and passes the view's end reads as torn although the file
-        // holds it whole.  Such a terminal is decoded again against the whole
-        // file: a record there is beyond this library's limit (CLY_ERR_ARG), not
-        // the io.EOF ReadLogRecord would not return.
+        *total += res[i].n_records;
         if (res[i].status == CLY_END_TORN) {
-            const uint64_t T = (uint64_t)res[i].end_offset, x0 = (T / PART_BYTES) * PART_BYTES;
-            if (files[i].len - x0 > VIEW_MAX) {
-                uint8_t hb[26] = {0};
-                const uint64_t nh = files[i].len - T < 26 ? files[i].len - T : 26;
-                HIPCK(hipMemcpy(hb, files[i].base + T, nh, hipMemcpyDeviceToHost));
-                const Hdr h = step_hdr((const uint8_t*)hb, 0, (int64_t)(files[i].len - T), (int64_t)T);
-                if (h.status == REC_OK) {
-                    fprintf(stderr, "clyscan: file %d: a record of %lld B at %llu crosses a part's 4-GiB view\n", i,
-                            (long long)h.size, (unsigned long long)T);
-                    return CLY_ERR_ARG;
-                }
-            }
+            const int rc = redecode_torn(files[i], i, (uint64_t)res[i].end_offset);
+            if (rc) return rc;
         }
     }
-    if (needed) *needed = c->h_g->total;
-    if (stats) {
-        stats->scan_ms = ms_scan + ms_emit; stats->resolve_ms = ms_link + ms_fix + ms_fin;
-        stats->total_ms = c->kms[5];
-        stats->passes = rounds;
-        stats->n_chunks = (uint32_t)(ntiles * CLY_NBLK * CLY_NL); stats->bytes = bytes; stats->records = total;
+    return CLY_OK;
+}
+
+// One attempt.  alloc == nullptr: the tuples go to `out`, and the host waits
+// once, after k_fin.  alloc != nullptr (cly_scan_device_alloc_internal): `out`
+// is ignored; the host waits for the link first and allocates *alloc for the
+// exact record count (scan_emit_alloc), after any repair rounds.
+static int scan_once(cly_ctx* c, const cly_file* files, int nfiles, ScanOut out, uint64_t* file_first,
+                     cly_file_result* res, uint64_t* needed, cly_stats* stats, hipStream_t st, cly_tuple** alloc,
+                     uint64_t* alloc_cap) {
+    cly_scan_state* s = c->scan;
+    if (alloc) { *alloc = nullptr; out.d_out = nullptr; out.cap = 0; }
+    if (nfiles == 0) { if (needed) *needed = 0; return CLY_OK; }
+    CLY_CK(hipSetDevice(c->device));
+    ScanGeom g;
+    int rc = ensure_files(s, nfiles);
+    if (rc || (rc = scan_plan(s, files, nfiles, &g)) || (rc = scan_reserve(s, nfiles, g))) return rc;
+    const bool detail = (s->dbg & 4) != 0;
+    if ((rc = scan_launch(s, st, nfiles, g, detail))) return rc;
+    // the nfix list the latest k_link wrote: [1] after the device's repair
+    // round, flipped by every host repair round (scan_repair)
+    int slot = 1;
+    if (!alloc) rc = scan_emit(s, st, nfiles, g, out, slot, detail);
+    else {
+        CLY_CK(hipMemcpyAsync(s->h_g, s->d_g, sizeof(Globals), hipMemcpyDeviceToHost, st));
+        CLY_CK(hipStreamSynchronize(st));
+        if (!s->h_g->nfix[slot] && !s->h_g->fail && !s->h_g->spill_over)
+            rc = scan_emit_alloc(s, st, nfiles, g, &out, slot, detail, alloc, alloc_cap);
     }
-    if (c->h_g->overflow || c->h_g->total > out_cap) return CLY_ERR_CAPACITY;
+    if (rc) return rc;
+    ScanTimes t = {0, 0, 0, 0, 0};
+    uint32_t rounds = 1, refixed = 0;
+    if (s->h_g->nfix[0]) { rounds++; refixed += s->h_g->nfix[0]; }          // the device round
+    if ((s->dbg & 2) && s->h_g->nfix[0])
+        fprintf(stderr, "clyscan: device repair round: %u tiles listed, longest walk %u from tile %u\n", s->h_g->nfix[0],
+                s->h_g->walk_max, (uint32_t)s->h_g->walk_dbg);
+    if (s->h_g->nfix[slot]) {
+        if ((rc = scan_repair(s, st, nfiles, &slot, &rounds, &refixed, &t.fix))) return rc;
+        if (!s->h_g->fail && !s->h_g->spill_over) {
+            // k_emit runs (again) for the repaired chains: ev[2] is re-recorded here (scan_times)
+            CLY_CK(hipEventRecord(s->ev[2], st));
+            rc = alloc ? scan_emit_alloc(s, st, nfiles, g, &out, slot, detail, alloc, alloc_cap)
+                       : scan_emit(s, st, nfiles, g, out, slot, detail);
+            if (rc) return rc;
+        }
+    }
+    if (s->h_g->spill_over) {                    // (k_emit / k_fin did not run: the caller runs the call again)
+        CLY_CK(hipStreamSynchronize(st));
+        CLY_CK(hipEventElapsedTime(&t.scan, s->ev[0], s->ev[1]));
+        s->kms[5] = t.scan + t.fix;
+        return CLY_OK;
+    }
+    if ((rc = scan_times(s, detail, &t))) return rc;
+    s->h_g->refix = refixed;
+    if (s->h_g->fail) {
+        fprintf(stderr, "clyscan: internal error (code %#x)\n", s->h_g->fail);
+        return CLY_ERR_DEVICE;
+    }
+    uint64_t total = 0;
+    if ((rc = scan_decode(s, files, nfiles, file_first, res, &total))) return rc;
+    if (needed) *needed = s->h_g->total;
+    if (stats) {
+        stats->scan_ms = t.scan + t.emit; stats->resolve_ms = t.link + t.fix + t.fin;
+        stats->total_ms = s->kms[5];
+        stats->passes = rounds;
+        stats->n_chunks = (uint32_t)(g.ntiles * CLY_NBLK * CLY_NL); stats->bytes = g.bytes; stats->records = total;
+    }
+    if (s->h_g->overflow || s->h_g->total > out.cap) return CLY_ERR_CAPACITY;
     return CLY_OK;
 }
 // One call: an attempt whose tiles needed more spill chunks than the pool
@@ -2790,20 +2851,23 @@ static int scan_attempt(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple
 static int scan_device(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple* d_out, uint64_t out_cap,
                        uint64_t* file_first, cly_file_result* res, uint64_t* needed, cly_stats* stats, void* stream_v,
                        cly_tuple** alloc, uint64_t* alloc_cap) {
+    if (!c || (!files && nfiles) || nfiles < 0 || !res || !file_first) return CLY_ERR_ARG;
+    cly_scan_state* s = c->scan;
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : c->stream;
     float discarded = 0;
     for (int attempt = 0;; attempt++) {
-        const int rc = scan_attempt(c, files, nfiles, d_out, out_cap, file_first, res, needed, stats, stream_v, alloc,
-                                    alloc_cap);
-        if (nfiles == 0 || !c->h_g->spill_over || (rc != CLY_OK && rc != CLY_ERR_CAPACITY)) {
-            c->kms[4] = discarded;
-            c->kms[5] += discarded;
+        const int rc = scan_once(c, files, nfiles, ScanOut{d_out, out_cap}, file_first, res, needed, stats, st, alloc,
+                                 alloc_cap);
+        if (nfiles == 0 || (rc != CLY_OK && rc != CLY_ERR_CAPACITY) || !s->h_g->spill_over) {
+            s->kms[4] = discarded;
+            s->kms[5] += discarded;
             return rc;
         }
-        discarded += c->kms[5];
+        discarded += s->kms[5];
         if (alloc && *alloc) { hipFree(*alloc); *alloc = nullptr; }
         if (attempt >= 3) return CLY_ERR_DEVICE;
-        const uint64_t want = (uint64_t)c->h_g->spill_next;
-        const int r2 = ensure_spill(c, std::max<uint64_t>(2ull * c->cap_spill, want + want / 4 + 64));
+        const uint64_t want = (uint64_t)s->h_g->spill_next;
+        const int r2 = ensure_spill(s, std::max<uint64_t>(2ull * s->cap_spill, want + want / 4 + 64));
         if (r2) return r2;
     }
 }
@@ -2812,180 +2876,170 @@ extern "C" int cly_scan_device(cly_ctx* c, const cly_file* files, int nfiles, cl
                                void* stream_v) {
     return scan_device(c, files, nfiles, d_out, out_cap, file_first, res, needed, stats, stream_v, nullptr, nullptr);
 }
-// The open's scan (clyload.hip; not in the public header): the tuple buffer
-// sized by the exact record count (*d_out, *cap slots; the caller frees it).
 extern "C" int cly_scan_device_alloc_internal(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple** d_out,
                                               uint64_t* cap, uint64_t* file_first, cly_file_result* res,
                                               uint64_t* needed) {
     if (!d_out) return CLY_ERR_ARG;
+    *d_out = nullptr;
     const int rc = scan_device(c, files, nfiles, nullptr, 0, file_first, res, needed, nullptr, nullptr, d_out, cap);
     if (rc != CLY_OK && *d_out) { hipFree(*d_out); *d_out = nullptr; }
     return rc;
 }
 
-// Host-memory entry.  Inputs of at least PIPE_MIN bytes go through a
-// pipeline: the files are split into groups of >= PIPE_GROUP bytes (whole
-// files); a copy thread moves group g+1 host->device while group g is scanned
-// and its tuples travel device->host (PCIe is full duplex), so the H2D stream
-// of the file bytes sets the pace.  On CLY_ERR_CAPACITY every group is still
-// scanned (nothing copied back) so that *needed is the exact record count.
+// Joins the thread when the scope ends, whichever way it ends
+struct JoinOnExit {
+    std::thread& t;
+    ~JoinOnExit() { if (t.joinable()) t.join(); }
+};
+
+// The groups of the host-memory pipeline: whole files, each group (but the
+// last) of >= PIPE_GROUP bytes, when the input has >= PIPE_MIN bytes at all;
+// group k is files gstart[k] .. gstart[k + 1] - 1
 #define PIPE_MIN (256ull << 20)
 #define PIPE_GROUP (512ull << 20)
+static std::vector<int> pipe_groups(const cly_file* files, int nfiles, uint64_t total) {
+    std::vector<int> gstart(1, 0);
+    uint64_t acc = 0;
+    for (int i = 0; i < nfiles; i++) {
+        acc += files[i].len;
+        if (total >= PIPE_MIN && acc >= PIPE_GROUP && i + 1 < nfiles) { gstart.push_back(i + 1); acc = 0; }
+    }
+    gstart.push_back(nfiles);
+    return gstart;
+}
+
+// The staging of the host-memory entry: d_bytes for `total` file bytes, d_tuples for `cap` tuples
+static int ensure_staging(cly_scan_state* s, uint64_t total, uint64_t cap) {
+    if (total + 4096 > s->cap_bytes) {
+        hipFree(s->d_bytes);
+        s->d_bytes = nullptr; s->cap_bytes = 0;
+        CLY_CK(hipMalloc(&s->d_bytes, total + 4096));
+        s->cap_bytes = total + 4096;
+    }
+    if (cap > s->cap_tuples) {
+        hipFree(s->d_tuples);
+        s->d_tuples = nullptr; s->cap_tuples = 0;
+        CLY_CK(hipMalloc(&s->d_tuples, sizeof(cly_tuple) * cap));
+        s->cap_tuples = cap;
+    }
+    return CLY_OK;
+}
+
+// Host-memory entry.  Inputs of at least PIPE_MIN bytes go through a
+// pipeline: the files are split into groups (pipe_groups); a copy thread
+// moves group g+1 host->device while group g is scanned and its tuples
+// travel device->host (PCIe is full duplex), so the H2D stream of the file
+// bytes sets the pace.  On CLY_ERR_CAPACITY every group is still scanned
+// (nothing copied back) so that *needed is the exact record count.
 extern "C" int cly_scan(cly_ctx* c, const cly_file* files, int nfiles, cly_tuple* out, uint64_t out_cap,
                         uint64_t* file_first, cly_file_result* res, uint64_t* needed, cly_stats* stats) {
     if (!c || (!files && nfiles) || nfiles < 0 || !res || !file_first) return CLY_ERR_ARG;
     if (nfiles == 0) { if (needed) *needed = 0; return CLY_OK; }
-    HIPCK(hipSetDevice(c->device));
+    cly_scan_state* s = c->scan;
+    CLY_CK(hipSetDevice(c->device));
     uint64_t total = 0;
     for (int i = 0; i < nfiles; i++) {
         if (files[i].len > MAX_FILE_LEN) return CLY_ERR_ARG;
         total += (files[i].len + 4095) & ~4095ULL;
     }
-    if (total + 4096 > c->cap_bytes) {
-        hipFree(c->d_bytes);
-        c->d_bytes = nullptr; c->cap_bytes = 0;
-        HIPCK(hipMalloc(&c->d_bytes, total + 4096));
-        c->cap_bytes = total + 4096;
-    }
-    const uint64_t cap = cly_scan_capacity(files, nfiles) + 16 * (uint64_t)nfiles + 16;
-    if (cap > c->cap_tuples) {
-        hipFree(c->d_tuples);
-        c->d_tuples = nullptr; c->cap_tuples = 0;
-        HIPCK(hipMalloc(&c->d_tuples, sizeof(cly_tuple) * cap));
-        c->cap_tuples = cap;
-    }
-    cly_file* df = (cly_file*)malloc(sizeof(cly_file) * nfiles);
-    uint64_t* goff = (uint64_t*)malloc(sizeof(uint64_t) * (nfiles + 1));   // device byte offset of each file
-    int* gstart = (int*)malloc(sizeof(int) * (nfiles + 1));
-    if (!df || !goff || !gstart) { free(df); free(goff); free(gstart); return CLY_ERR_DEVICE; }
+    int rc = ensure_staging(s, total, cly_scan_capacity(files, nfiles) + 16 * (uint64_t)nfiles + 16);
+    if (rc) return rc;
+    std::vector<cly_file> df;
+    std::vector<uint64_t> goff;                  // device byte offset of each file
+    std::vector<int> gstart;
+    try {
+        df.assign(files, files + nfiles);
+        goff.resize(nfiles + 1);
+        gstart = pipe_groups(files, nfiles, total);
+    } catch (const std::bad_alloc&) { return CLY_ERR_DEVICE; }
     {
         uint64_t off = 0;
         for (int i = 0; i < nfiles; i++) {
-            df[i] = files[i];
-            df[i].base = c->d_bytes + off;
+            df[i].base = s->d_bytes + off;
             goff[i] = off;
             off += (files[i].len + 4095) & ~4095ULL;
         }
         goff[nfiles] = off;
     }
-    int ng = 0;
-    {
-        uint64_t acc = 0;
-        gstart[ng++] = 0;
-        for (int i = 0; i < nfiles; i++) {
-            acc += files[i].len;
-            if (total >= PIPE_MIN && acc >= PIPE_GROUP && i + 1 < nfiles) { gstart[ng++] = i + 1; acc = 0; }
-        }
-        gstart[ng] = nfiles;
-    }
-    // the copy thread: group after group, each fully on the device before `ready` moves on
-    std::atomic<int> ready(0), copy_err(0);
-    std::thread copier([&]() {
-        if (hipSetDevice(c->device) != hipSuccess) { copy_err = 1; ready = ng; return; }
-        for (int g = 0; g < ng; g++) {
-            for (int i = gstart[g]; i < gstart[g + 1]; i++)
-                if (files[i].len && hipMemcpy(c->d_bytes + goff[i], files[i].base, files[i].len,
-                                              hipMemcpyHostToDevice) != hipSuccess) copy_err = 1;
-            ready.store(g + 1, std::memory_order_release);
-        }
-    });
-    int rc = CLY_OK;
+    const int ng = (int)gstart.size() - 1;
     uint64_t tbase = 0, o = 0, need = 0;
     bool over = false;
     cly_stats st_acc;
     memset(&st_acc, 0, sizeof(st_acc));
-    for (int g = 0; g < ng && (rc == CLY_OK || rc == CLY_ERR_CAPACITY); g++) {
-        while (ready.load(std::memory_order_acquire) <= g) std::this_thread::yield();
-        if (copy_err) { rc = CLY_ERR_DEVICE; break; }
-        const int f0 = gstart[g], nf = gstart[g + 1] - gstart[g];
-        const uint64_t gcap = cly_scan_capacity(files + f0, nf) + 16;
-        uint64_t slots = 0;
-        cly_stats sg;
-        cly_tuple* gout = c->d_tuples + tbase;
-        cly_tuple* big = nullptr;            // a group of exotic (< 9 B) records: its own buffer
-        int r = cly_scan_device(c, df + f0, nf, gout, gcap, file_first + f0, res + f0, &slots, &sg, nullptr);
-        if (r == CLY_ERR_CAPACITY && slots > gcap) {
-            if (hipStreamSynchronize(c->stream) != hipSuccess || hipMalloc(&big, sizeof(cly_tuple) * (slots + 16)) != hipSuccess) {
-                rc = CLY_ERR_DEVICE; break;
+    {
+        // the copy thread: group after group, each fully on the device before `ready` moves on
+        std::atomic<int> ready(0), copy_err(0);
+        std::thread copier([&]() {
+            if (hipSetDevice(c->device) != hipSuccess) { copy_err = 1; ready = ng; return; }
+            for (int g = 0; g < ng; g++) {
+                for (int i = gstart[g]; i < gstart[g + 1]; i++)
+                    if (files[i].len && hipMemcpy(s->d_bytes + goff[i], files[i].base, files[i].len,
+                                                  hipMemcpyHostToDevice) != hipSuccess) copy_err = 1;
+                ready.store(g + 1, std::memory_order_release);
             }
-            gout = big;
-            r = cly_scan_device(c, df + f0, nf, gout, slots + 16, file_first + f0, res + f0, &slots, &sg, nullptr);
+        });
+        JoinOnExit joined{copier};
+        for (int g = 0; g < ng && (rc == CLY_OK || rc == CLY_ERR_CAPACITY); g++) {
+            while (ready.load(std::memory_order_acquire) <= g) std::this_thread::yield();
+            if (copy_err) { rc = CLY_ERR_DEVICE; break; }
+            const int f0 = gstart[g], nf = gstart[g + 1] - gstart[g];
+            const uint64_t gcap = cly_scan_capacity(files + f0, nf) + 16;
+            uint64_t slots = 0;
+            cly_stats sg;
+            cly_tuple* gout = s->d_tuples + tbase;
+            cly_tuple* big = nullptr;            // a group of exotic (< 9 B) records: its own buffer
+            int r = cly_scan_device(c, df.data() + f0, nf, gout, gcap, file_first + f0, res + f0, &slots, &sg, nullptr);
+            if (r == CLY_ERR_CAPACITY && slots > gcap) {
+                if (hipStreamSynchronize(c->stream) != hipSuccess ||
+                    hipMalloc(&big, sizeof(cly_tuple) * (slots + 16)) != hipSuccess) {
+                    rc = CLY_ERR_DEVICE; break;
+                }
+                gout = big;
+                r = cly_scan_device(c, df.data() + f0, nf, gout, slots + 16, file_first + f0, res + f0, &slots, &sg,
+                                    nullptr);
+            }
+            if (r != CLY_OK) { hipFree(big); rc = r; break; }
+            st_acc.scan_ms += sg.scan_ms; st_acc.resolve_ms += sg.resolve_ms; st_acc.total_ms += sg.total_ms;
+            st_acc.passes = st_acc.passes > sg.passes ? st_acc.passes : sg.passes;
+            st_acc.n_chunks += sg.n_chunks; st_acc.bytes += sg.bytes; st_acc.records += sg.records;
+            // tuples of the group's files back to host memory (per file: the slots may hold
+            // tuples past an ErrInvalidCRC), while the next group is still coming in
+            for (int i = f0; i < f0 + nf; i++) {
+                need += res[i].n_records;
+                if (over || need > out_cap) { over = true; rc = CLY_ERR_CAPACITY; continue; }
+                if (res[i].n_records &&
+                    hipMemcpyAsync(out + o, gout + file_first[i], sizeof(cly_tuple) * res[i].n_records,
+                                   hipMemcpyDeviceToHost, c->stream) != hipSuccess) { rc = CLY_ERR_DEVICE; break; }
+                file_first[i] = o;
+                o += res[i].n_records;
+            }
+            if (big) { if (hipStreamSynchronize(c->stream) != hipSuccess) rc = CLY_ERR_DEVICE; hipFree(big); }
+            tbase += gcap;
         }
-        if (r != CLY_OK) { hipFree(big); rc = r; break; }
-        st_acc.scan_ms += sg.scan_ms; st_acc.resolve_ms += sg.resolve_ms; st_acc.total_ms += sg.total_ms;
-        st_acc.passes = st_acc.passes > sg.passes ? st_acc.passes : sg.passes;
-        st_acc.n_chunks += sg.n_chunks; st_acc.bytes += sg.bytes; st_acc.records += sg.records;
-        // tuples of the group's files back to host memory (per file: the slots may hold
-        // tuples past an ErrInvalidCRC), while the next group is still coming in
-        for (int i = f0; i < f0 + nf; i++) {
-            need += res[i].n_records;
-            if (over || need > out_cap) { over = true; rc = CLY_ERR_CAPACITY; continue; }
-            if (res[i].n_records &&
-                hipMemcpyAsync(out + o, gout + file_first[i], sizeof(cly_tuple) * res[i].n_records,
-                               hipMemcpyDeviceToHost, c->stream) != hipSuccess) { rc = CLY_ERR_DEVICE; break; }
-            file_first[i] = o;
-            o += res[i].n_records;
-        }
-        if (big) { if (hipStreamSynchronize(c->stream) != hipSuccess) rc = CLY_ERR_DEVICE; hipFree(big); }
-        tbase += gcap;
-    }
-    if (rc != CLY_OK && rc != CLY_ERR_CAPACITY) ready.store(ng);
-    copier.join();                                // no return before this: the copier must be joined
+    }                                             // (the copier is joined here)
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == CLY_OK) rc = CLY_ERR_DEVICE;
-    free(df); free(goff); free(gstart);
     if (stats) *stats = st_acc;
     if (needed) *needed = need;
     return rc;
 }
 
-// Context accessors for the merge / index entries (clymerge.hip, clyindex.hip); not in the public header.
-extern "C" hipStream_t cly_ctx_stream_internal(cly_ctx* c) { return c->stream; }
-extern "C" int64_t cly_ctx_now_internal(cly_ctx* c) {
-    if (c->now_ns) return c->now_ns;
-    struct timespec ts;
-    clock_gettime(CLOCK_REALTIME, &ts);
-    return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
-}
-extern "C" void cly_ctx_set_clock(cly_ctx* c, int64_t now_ns) { if (c) c->now_ns = now_ns; }
-extern "C" int cly_ctx_device_internal(cly_ctx* c) { return c->device; }
-extern "C" void** cly_ctx_merge_slot_internal(cly_ctx* c) { return &c->merge_scratch; }
-
 // Per-kernel times of the last cly_scan_device call (ms): k_scan, link rounds
-// (k_link + repair), k_emit, k_fin, k_ovf, all.  Not in the public header.
-// Debug (not in the public header): flags (bit 0: snapshot k_scan's tile
-// LOCALs); cly_dbg_tiles copies the snapshot (32 B per tile) and the final
-// TileIns (32 B per tile) of the last call to host memory.
-extern "C" void cly_dbg_set(cly_ctx* c, int flags) { c->dbg = flags; }
+// (k_link + repair), k_emit, k_fin, discarded attempts, all.
+// Debug flags (bit 0: snapshot k_scan's tile LOCALs); cly_dbg_tiles copies the
+// snapshot (32 B per tile) and the final TileIns (32 B per tile) of the last
+// call to host memory.  None of these is in the public header.
+extern "C" void cly_dbg_set(cly_ctx* c, int flags) { c->scan->dbg = flags; }
 extern "C" int cly_dbg_tiles(cly_ctx* c, void* loc_out, void* tin_out, int64_t ntiles) {
-    HIPCK(hipSetDevice(c->device));
-    if (loc_out && c->d_dbg && ntiles <= c->cap_dbg)
-        HIPCK(hipMemcpy(loc_out, c->d_dbg, sizeof(TileLocal) * ntiles, hipMemcpyDeviceToHost));
-    if (tin_out && ntiles <= c->cap_tiles) HIPCK(hipMemcpy(tin_out, c->d_tin, sizeof(TileIn) * ntiles, hipMemcpyDeviceToHost));
+    cly_scan_state* s = c->scan;
+    CLY_CK(hipSetDevice(c->device));
+    if (loc_out && s->d_dbg && ntiles <= s->cap_dbg)
+        CLY_CK(hipMemcpy(loc_out, s->d_dbg, sizeof(TileLocal) * ntiles, hipMemcpyDeviceToHost));
+    if (tin_out && ntiles <= s->cap_tiles) CLY_CK(hipMemcpy(tin_out, s->d_tin, sizeof(TileIn) * ntiles, hipMemcpyDeviceToHost));
     return CLY_OK;
 }
 extern "C" int cly_dbg_kernel_ms(cly_ctx* c, double* out6) {
-    for (int i = 0; i < 6; i++) out6[i] = c->kms[i];
+    for (int i = 0; i < 6; i++) out6[i] = c->scan->kms[i];
     return 6;
-}
-
-extern "C" const char* cly_strerror(int code) {
-    switch (code) {
-        case CLY_END_EOF: return "ok / io.EOF";
-        case CLY_END_ZERO: return "io.EOF (zero header)";
-        case CLY_END_TORN: return "io.EOF (torn record)";
-        case CLY_ERR_CRC: return "invalid crc value, logRecord maybe corrupted";
-        case CLY_ERR_TRUNC5: return "5-byte tail: header decode index out of range";
-        case CLY_ERR_VARINT: return "varint overflow: header slice bounds out of range";
-        case CLY_ERR_OFFSET: return "mmap: invalid ReadAt offset";
-        case CLY_ERR_CAPACITY: return "output capacity too small";
-        case CLY_ERR_DEVICE: return "HIP device error";
-        case CLY_ERR_ARG: return "invalid argument";
-        case CLY_ERR_NOREPAIR: return "internal: chain resolution failed";
-        case -14: return "the data dir maybe contaminated or damaged";            // CLY_ERR_DIR (clyload.h)
-        case -15: return "merge-finished: no readable record / value not an integer";   // CLY_ERR_MERGE_FIN
-        case -16: return "the key can not be empty";                              // CLY_ERR_KEY_EMPTY (clyload.h)
-        default: return "unknown status";
-    }
 }
 
 #ifndef CLY_SRC_HASH

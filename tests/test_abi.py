@@ -5,6 +5,7 @@ No kernel is launched here."""
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -39,6 +40,37 @@ def test_library_exports_header_symbols(header, lib):
         assert hasattr(h, n), "%s missing from %s" % (n, lib)
     expect = {"clyscan.h": _abi.SCAN_SYMBOLS, "clyload.h": _abi.LOAD_SYMBOLS}.get(header, _abi.GEN_SYMBOLS)
     assert sorted(expect) == names
+
+
+# Exports of libclyscan.so that no header in include/ declares.  A new private
+# export has to be added here on purpose.
+PRIVATE_EXPORTS = {
+    # debug hooks of the tests and tools
+    "cly_dbg_set", "cly_dbg_tiles", "cly_dbg_kernel_ms", "cly_dbg_read_host",
+    # calls between the library's own translation units (couloydb_amd/csrc/cly_internal.h)
+    "cly_scratch_internal", "cly_scan_state_create_internal", "cly_scan_state_destroy_internal",
+    "cly_scan_device_alloc_internal", "cly_order_keys_internal", "cly_ix_hash_mask_internal",
+}
+
+
+def exported_cly_symbols(path):
+    tool = shutil.which("nm") or shutil.which("llvm-nm")
+    assert tool, "neither nm nor llvm-nm is installed"
+    out = subprocess.check_output([tool, "-D", "--defined-only", path]).decode()
+    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("cly_")}
+
+
+@pytest.mark.parametrize("lib", ["libclyscan.so", "libclyscan_small.so"])
+def test_exported_surface_is_pinned(lib):
+    path = _abi.lib_path(lib)
+    assert os.path.exists(path), "build the libraries first (__graft_entry__.build())"
+    public = set()
+    for header in ("clyscan.h", "clyload.h", "clyread.h"):
+        public |= set(declared_functions(header))
+    assert not public & PRIVATE_EXPORTS
+    got = exported_cly_symbols(path)
+    assert got - public - PRIVATE_EXPORTS == set(), "exports that are neither declared in include/ nor listed"
+    assert (public | PRIVATE_EXPORTS) - got == set(), "declared or listed, but not exported"
 
 
 def test_struct_layouts():

@@ -453,3 +453,24 @@ def test_host_entry_and_wrapper(scanner):
     assert bad.record(3).key == recs[6][2][0]
     with pytest.raises(ScanError):
         scanner.read([DataFile(d, 3)], [(3, -1)]).record(0)
+
+
+@gpu
+@pytest.mark.parametrize("lib", LIBS)
+def test_context_lifetime(lib):
+    """Four contexts in turn in one process, each created, used for one scan
+    and one read (the scan's state and the scratch arena both grow from
+    nothing) and destroyed: every round returns what the first returned."""
+    data = np.fromfile(os.path.join(GOLD, "zero_tail.cly"), np.uint8)
+    rounds = []
+    for _ in range(4):
+        with Scanner(0, lib=lib) as sc:
+            r = sc.scan([DataFile(data, 7)])
+            pos = make_pos([(7, int(o)) for o in r.tuples["offset"]] + [(7, int(r.end_offset[0])), (8, 0)])
+            rd = sc.read([DataFile(data, 7)], pos)
+            rounds.append((r.tuples.tobytes(), list(r.status), list(r.n_records), list(r.end_offset),
+                           rd.tuples.tobytes(), rd.status.tobytes(), rd.val_off.tobytes(), rd.values.tobytes()))
+    assert len(r.tuples) >= 10 and (rd.status[:-2] == REC).all() and rd.status[-1] == NOFILE
+    assert (rd.tuples[:-2].view(np.uint8) == r.tuples.view(np.uint8)).all()
+    for k in range(1, 4):
+        assert rounds[k] == rounds[0], "round %d differs from the first" % k

@@ -45,10 +45,10 @@ PATCHES["cnt"] = [
         if (!bm) return L;""", """        const u64 bm = __ballot(bad);
         if (!bm) return L;
         if (lane == 0) atomicAdd((unsigned long long*)&g->walk_dbg, 1ull);"""),
-    ("""    float ms_scan = 0, ms_link = 0, ms_emit = 0, ms_fin = 0;""",
-     """    fprintf(stderr, "xp: general-pass blocks %u, agreement rounds %llu\\n", c->h_g->rounds,
-            (unsigned long long)c->h_g->walk_dbg);
-    float ms_scan = 0, ms_link = 0, ms_emit = 0, ms_fin = 0;"""),
+    ("""    if ((rc = scan_times(s, detail, &t))) return rc;""",
+     """    fprintf(stderr, "xp: general-pass blocks %u, agreement rounds %llu\\n", s->h_g->rounds,
+            (unsigned long long)s->h_g->walk_dbg);
+    if ((rc = scan_times(s, detail, &t))) return rc;"""),
 ]
 # the stride round repeated while it takes a full 64 records and the chain stays in the block
 PATCHES["sloop"] = [
@@ -102,11 +102,11 @@ PATCHES["prof"] = [
     ("""        const u64 bm = __ballot(bad);
         if (!bm) return L;""", """        const u64 bm = __ballot(bad);
         if (!bm) { if (lane == 0 && iter) atomicAdd((unsigned long long*)&g->walk_dbg, (unsigned long long)iter << 40); return L; }"""),
-    ("""    float ms_scan = 0, ms_link = 0, ms_emit = 0, ms_fin = 0;""",
+    ("""    if ((rc = scan_times(s, detail, &t))) return rc;""",
      """    fprintf(stderr, "xp: guess %llu pred %llu gen-walk %llu resolve %llu gen-out %llu crc %llu stage %llu | general blocks %llu resolve iters %llu\\\\n",
-            c->h_g->xp_t[0], c->h_g->xp_t[1], c->h_g->xp_t[2], c->h_g->xp_t[3], c->h_g->xp_t[4], c->h_g->xp_t[5],
-            c->h_g->xp_t[6], c->h_g->xp_t[7], (unsigned long long)(c->h_g->walk_dbg >> 40));
-    float ms_scan = 0, ms_link = 0, ms_emit = 0, ms_fin = 0;"""),
+            s->h_g->xp_t[0], s->h_g->xp_t[1], s->h_g->xp_t[2], s->h_g->xp_t[3], s->h_g->xp_t[4], s->h_g->xp_t[5],
+            s->h_g->xp_t[6], s->h_g->xp_t[7], (unsigned long long)(s->h_g->walk_dbg >> 40));
+    if ((rc = scan_times(s, detail, &t))) return rc;"""),
 ]
 # every tile's loads read its part's first tile (L2-resident): k_scan's time with
 # the HBM latency taken out, same record work (timing only)
@@ -164,8 +164,8 @@ def build(name):
             s = s.replace(old, new)
         open(p, "w").write(s)
         out = os.path.join(ROOT, "couloydb_amd", "libexp_%s.so" % name)
-        srcs = [f for f in ["clyscan.hip", "clymerge.hip", "clyindex.hip", "clyload.hip", "clyorder.hip"]
-                if os.path.exists(os.path.join(os.path.dirname(p), f))]
+        # the product sources: every translation unit of libclyscan.so (clygen.hip is the writer's own library)
+        srcs = sorted(f for f in os.listdir(os.path.dirname(p)) if f.endswith(".hip") and f != "clygen.hip")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                                "-w", "-DCLY_SRC_HASH=\"xp-%s\"" % name, "-o", out] + srcs,
                               cwd=os.path.dirname(p))
